@@ -4,12 +4,25 @@ bert-base-uncased + ViT-B/16 + fusion head, forward + backward + AdamW, bs=256 p
 GPU, RCCL gradient all-reduce). Prints ONE JSON line on rank 0.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 256] [--precision fp32|bf16]
-                  [--mode finetune|frozen] [--no-cpu-baseline] [--no-bf16]
+                  [--mode finetune|frozen] [--full [--no-cpu-baseline] [--no-bf16]] [--dump-outputs DIR]
                   [--workload train|forward|extract|retrieve|preprocess|latency|preembed|preembed_image]
 
-The train headline is fp32 (the reference's arithmetic; logits within 1e-3 of the CPU oracle); the
-same step in bf16 (bf16 MFMA operands, fp32 accumulation and master weights) is reported beside it
-under "bf16". `--gpus N` outside a torch.distributed launcher starts N ranks itself.
+A plain run does what the headline needs and no more: set-up, `--warmup` untimed steps, `--steps`
+timed steps, the result line (metric, value, unit, higher_is_better, dtype, ms_per_step and what the
+timed steps give for free). `--full` adds every other measurement and check: the per-GEMM probe
+steps and the roofline line, the same step in bf16 (bf16 MFMA operands, fp32 accumulation and master
+weights; reported under "bf16"), the CPU baselines with the logit deviation from the CPU oracle, the
+first-step / final-loss comparison with the oracle's fixtures, and the secondary figures of the other
+workloads (end-to-end corpus build, per-kernel rates, eager latency). `--no-cpu-baseline` and
+`--no-bf16` trim a `--full` run.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller as DIR/<name>.npy
+(float32; at most 64 MB in all, a fixed seeded sample of anything larger; rank 0). Weights, inputs
+and dropout seeds are fixed by the arguments, so two builds run with the same arguments can be
+compared file for file.
+
+The train headline is fp32 (the reference's arithmetic; logits within 1e-3 of the CPU oracle).
+`--gpus N` outside a torch.distributed launcher starts N ranks itself.
 """
 import argparse
 import json
@@ -47,6 +60,44 @@ def host_cores():
 def log(msg):
     """progress on stderr (the JSON line on stdout stays the only stdout output)"""
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
+
+
+DUMP_BYTES = 48 << 20  # --dump-outputs: all files together stay below this (the limit is 64 MB)
+
+
+def _named_tensors(name, obj):
+    """(name, tensor) for every tensor in a step's result: a tensor, or nested tuples / lists /
+    dicts of them, or an object carrying them as attributes (a model output record)"""
+    if torch.is_tensor(obj):
+        yield name, obj
+    elif isinstance(obj, dict):
+        for k, v in obj.items():
+            yield from _named_tensors(f"{name}_{k}", v)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            yield from _named_tensors(f"{name}_{i}", v)
+    elif hasattr(obj, "__dict__"):
+        for k, v in vars(obj).items():
+            yield from _named_tensors(f"{name}_{k}", v)
+
+
+def dump_outputs(path, rank, **outputs):
+    """`--dump-outputs`: every tensor of `outputs` as <path>/<name>.npy in float32 (rank 0 only). An
+    array over its share of DUMP_BYTES is cut to a fixed sample of its flattened elements (indices
+    from a generator seeded with 0, ascending), the same elements in every run."""
+    if not path or rank != 0:
+        return
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    items = [(n, t) for name, obj in outputs.items() for n, t in _named_tensors(name, obj)]
+    share = DUMP_BYTES // 4 // max(1, len(items))
+    for n, t in items:
+        t = t.detach()
+        if t.numel() > share:
+            idx = torch.randint(0, t.numel(), (share,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(path, n + ".npy"), t.float().cpu().numpy())
+    log(f"dumped {len(items)} arrays to {path}")
 
 
 def _timed(fn, steps):
@@ -162,10 +213,10 @@ def pmc_traffic(kernel):
 GFLOP_RESNET50, GFLOP_MPNET128 = 8.174, 22.35  # per image @224 / per sequence @L=128
 
 
-def extract_leg(args, dev, world, rank, precision):
+def extract_leg(args, dev, world, rank, precision, dump=False):
     """`--warmup` + `--steps` timed extractor steps of one precision on HBM-resident synthetic
     inputs (a step = `--batch` images through ResNet50 + `--batch` texts through MPNet at L=128),
-    then the per-GEMM device times of one eager step (GemmProbe) for the roofline line."""
+    then (`--full`) the per-GEMM device times of one eager step (GemmProbe) for the roofline line."""
     from mmfd import kernels as K
     from mmfd.encoders import MPNetConfig, MPNetModel
     from mmfd.evidence import SentenceEncoder, resnet50
@@ -195,9 +246,9 @@ def extract_leg(args, dev, world, rank, precision):
     t0 = time.perf_counter()
     for _ in range(args.steps):
         e0.record()
-        img(px)
+        f = img(px)
         e1.record()
-        enc.encode_ids(ids, mask, batch_size=args.batch)
+        e = enc.encode_ids(ids, mask, batch_size=args.batch)
         e2.record()
         e2.synchronize()
         t_img += e0.elapsed_time(e1)
@@ -211,6 +262,16 @@ def extract_leg(args, dev, world, rank, precision):
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = t.item()
+    ips = args.batch * args.steps / (t_img * 1e-3)
+    tps = args.batch * args.steps / (t_txt * 1e-3)
+    step_tf = args.batch * args.steps * (GFLOP_RESNET50 + GFLOP_MPNET128) / ((t_img + t_txt) * 1e-3) / 1e3
+    res = {"items": 2 * args.batch * world * args.steps / elapsed, "ms": 1000.0 * elapsed / args.steps,
+           "ips": ips, "tps": tps, "step_tflops": step_tf}
+    if dump:
+        dump_outputs(args.dump_outputs, rank, image_features=f, text_embeddings=e)
+    if not args.full:
+        del img, enc
+        return res
     probe = K.GemmProbe()
     with probe:
         step()
@@ -220,12 +281,8 @@ def extract_leg(args, dev, world, rank, precision):
     x6 = "_x6f" in dom_name or dom_name.rstrip().endswith("true>")
     peak = PEAK_TFLOPS[precision] if not x6 else PEAK_TFLOPS["bf16"] / 6
     traffic, traffic_src = pmc_traffic(dom_name)
-    ips = args.batch * args.steps / (t_img * 1e-3)
-    tps = args.batch * args.steps / (t_txt * 1e-3)
-    step_tf = args.batch * args.steps * (GFLOP_RESNET50 + GFLOP_MPNET128) / ((t_img + t_txt) * 1e-3) / 1e3
     del img, enc
-    return {"items": 2 * args.batch * world * args.steps / elapsed, "ms": 1000.0 * elapsed / args.steps,
-            "ips": ips, "tps": tps, "step_tflops": step_tf,
+    return {**res,
             "roofline": {"bound": "mfma", "kernel": dom_name, "achieved": round(achieved, 1), "peak": round(peak, 1),
                          "unit": "TFLOP/s", "frac": round(achieved / peak, 4), "traffic": traffic,
                          "traffic_unit": "bytes/launch", "traffic_source": traffic_src,
@@ -350,15 +407,15 @@ def extract_main(args, dev, world, rank):
     and MPNet CLS text embeddings at L=128 (text2text_retrieval.py:129-157), eval mode, random-init
     weights, fp32 (the reference's precision) with bf16 beside it; the headline times inputs
     resident in HBM (each rank its own shard, no collective), `e2e` the product API from files."""
-    res = extract_leg(args, dev, world, rank, args.precision)
+    res = extract_leg(args, dev, world, rank, args.precision, dump=True)
     log(f"extract {args.precision}: {res['items']:.1f} items/s")
     sec = None
-    if args.precision == "fp32" and not args.no_bf16:
+    if args.full and args.precision == "fp32" and not args.no_bf16:
         torch.cuda.empty_cache()
         sec = extract_leg(args, dev, world, rank, "bf16")
         log(f"extract bf16: {sec['items']:.1f} items/s")
     e2e = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             e2e = extract_e2e(dev, args.precision)
             log(f"extract e2e: {e2e}")
@@ -375,19 +432,20 @@ def extract_main(args, dev, world, rank):
             "images_per_s_per_gpu": round(res["ips"], 1), "texts_per_s_per_gpu": round(res["tps"], 1),
             "image_tflops": round(res["ips"] * GFLOP_RESNET50 / 1e3, 1),
             "text_tflops": round(res["tps"] * GFLOP_MPNET128 / 1e3, 1),
-            "roofline": res["roofline"],
             "roofline_step_frac": round(res["step_tflops"] / step_peak(args.precision)[0], 4),
             "roofline_step_peak": {"peak": round(step_peak(args.precision)[0], 1), "unit": "TFLOP/s",
                                    "note": step_peak(args.precision)[1] + f"; {GFLOP_RESNET50} GFLOP/image, "
                                            f"{GFLOP_MPNET128} GFLOP/text (SURVEY 8(d))"},
         }
+        if args.full:
+            out["roofline"] = res["roofline"]
         if sec is not None:
             out["bf16"] = {"value": round(sec["items"], 1), "unit": "items/s",
                            "images_per_s_per_gpu": round(sec["ips"], 1), "texts_per_s_per_gpu": round(sec["tps"], 1),
                            "roofline": sec["roofline"]}
         if e2e is not None:
             out["e2e"] = e2e
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = extract_cpu_baseline()
             except Exception as e:
@@ -422,7 +480,7 @@ def retrieve_main(args, dev, world, rank):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        found = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -432,26 +490,30 @@ def retrieve_main(args, dev, world, rank):
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = t.item()
-    # dominant kernel: the score pass, timed with events on the launch stream (torch's current)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    reps = 20
-    e0.record()
-    for _ in range(reps):
-        sc = K.cosine_scores(q, index.emb, mode=K.COS_PAIR, eps=1e-6)
-    e1.record()
-    torch.cuda.synchronize()
-    passes = (args.batch + 7) // 8  # one corpus pass per 8-query tile
-    score_ms = e0.elapsed_time(e1) / reps
-    algo_bytes = passes * N * D * 4 + args.batch * N * 4  # corpus read per pass + scores written
-    e0.record()
-    for _ in range(reps):
-        K.topk(sc, 2 * top_k)
-    e1.record()
-    torch.cuda.synchronize()
-    topk_ms = e0.elapsed_time(e1) / reps
+    if args.dump_outputs:  # [(index, score)] per query -> two [batch, top_k] arrays (short rows padded: -1, 0)
+        pad = [r + [(-1, 0.0)] * (top_k - len(r)) for r in found]
+        dump_outputs(args.dump_outputs, rank, indices=torch.tensor([[i for i, _ in r] for r in pad]),
+                     scores=torch.tensor([[v for _, v in r] for r in pad], dtype=torch.float64))
+    if args.full:
+        # dominant kernel: the score pass, timed with events on the launch stream (torch's current)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        reps = 20
+        e0.record()
+        for _ in range(reps):
+            sc = K.cosine_scores(q, index.emb, mode=K.COS_PAIR, eps=1e-6)
+        e1.record()
+        torch.cuda.synchronize()
+        passes = (args.batch + 7) // 8  # one corpus pass per 8-query tile
+        score_ms = e0.elapsed_time(e1) / reps
+        algo_bytes = passes * N * D * 4 + args.batch * N * 4  # corpus read per pass + scores written
+        e0.record()
+        for _ in range(reps):
+            K.topk(sc, 2 * top_k)
+        e1.record()
+        torch.cuda.synchronize()
+        topk_ms = e0.elapsed_time(e1) / reps
     if rank == 0:
         qps = args.batch * world * args.steps / elapsed
-        achieved = algo_bytes / (score_ms * 1e-3) / 1e9
         out = {
             "metric": "evidence retrieval queries/sec (cosine top-50, distinct scores)", "value": round(qps, 1),
             "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -459,12 +521,14 @@ def retrieve_main(args, dev, world, rank):
             "vs_baseline": None, "dtype": "f32", "data": "synthetic (non-negative features)",
             "config": {"workload": "retrieval scoring (SURVEY 8f row 2): 41,256 x 2048 fp32 image corpus, top_k 50",
                        "global_batch": args.batch * world, "parallelism": f"shard{world}"},
-            "roofline": {"bound": "hbm", "kernel": "cosine_scores_kernel<float>", "achieved": round(achieved, 1),
-                         "peak": 8000.0, "unit": "GB/s", "frac": round(achieved / 8000.0, 4), "traffic": None,
-                         "algorithmic_bytes_per_launch": algo_bytes, "avg_launch_us": round(1000 * score_ms, 2)},
-            "topk_us": round(1000 * topk_ms, 2),
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full:
+            achieved = algo_bytes / (score_ms * 1e-3) / 1e9
+            out["roofline"] = {"bound": "hbm", "kernel": "cosine_scores_kernel<float>", "achieved": round(achieved, 1),
+                               "peak": 8000.0, "unit": "GB/s", "frac": round(achieved / 8000.0, 4), "traffic": None,
+                               "algorithmic_bytes_per_launch": algo_bytes, "avg_launch_us": round(1000 * score_ms, 2)}
+            out["topk_us"] = round(1000 * topk_ms, 2)
+        if args.full and not args.no_cpu_baseline and world == 1:
             from oracle.retrieval import cosine_pair, retrieve_unique
             fc, qc = feats.numpy(), q[:2].cpu().numpy()
             t1 = time.perf_counter()
@@ -497,7 +561,7 @@ def forward_main(args, dev, world, rank):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        tr.predict(batch)
+        logits = tr.predict(batch)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -507,6 +571,7 @@ def forward_main(args, dev, world, rank):
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = t.item()
+    dump_outputs(args.dump_outputs, rank, logits=logits)
     if rank == 0:
         pairs = args.batch * world * args.steps / elapsed
         tf = pairs / world * 117.21e9 / 1e12  # 117.21 GFLOP/pair forward
@@ -557,6 +622,7 @@ def preprocess_main(args, dev, world, rank):
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = t.item()
+    dump_outputs(args.dump_outputs, rank, pixel_values=out)
     if rank == 0:
         per = e0.elapsed_time(e1) / args.steps * 1e-3
         oh, ow = 256, 341
@@ -574,7 +640,7 @@ def preprocess_main(args, dev, world, rank):
                               "achieved": round(achieved, 1), "peak": 8000.0, "unit": "GB/s",
                               "frac": round(achieved / 8000.0, 4), "traffic": None,
                               "algorithmic_bytes_per_launch": algo * args.batch, "avg_launch_us": round(per * 1e6, 2)}}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             from PIL import Image
             from oracle.preprocess import preprocess
             from mmfd.preprocess import MODES
@@ -611,7 +677,7 @@ def latency_main(args, dev, world, rank):
 
     c, e = pair(), pair()
     res = {}
-    for mode in ("eager", "graph"):
+    for mode in ("eager", "graph") if args.full else ("graph",):
         pr = PairPredictor.from_trainer(tr, use_graph=mode == "graph")
         for _ in range(max(1, args.warmup)):
             pr.predict_logits(*c, *e)
@@ -621,7 +687,7 @@ def latency_main(args, dev, world, rank):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            pr.predict_logits(*c, *e)
+            logits = pr.predict_logits(*c, *e)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -631,6 +697,7 @@ def latency_main(args, dev, world, rank):
         if world > 1:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         res[mode] = t.item() / args.steps * 1e3
+    dump_outputs(args.dump_outputs, rank, logits=logits)  # (of the graph replay, the timed path)
     if rank == 0:
         # algorithmic forward FLOPs of the pair at L=512 (FlopCounterMode-style matmul count):
         # BERT 2 x (12 x (4 x 512 x 768^2 x 2 + 2 x 512 x 768 x 3072 x 2 + 2 x 512^2 x 768 x 2)),
@@ -645,8 +712,9 @@ def latency_main(args, dev, world, rank):
                "config": {"workload": "single-pair inference (SURVEY 8f row 4): bert-base-uncased + ViT-B/16 + "
                                       "fusion head, HIP graph replay", "global_batch": 1, "seq_len": L,
                           "image_size": 224, "parallelism": f"replicas{world}"},
-               "eager_ms_per_pair": round(res["eager"], 3),
                "tflops_graph": round(flops / (res["graph"] * 1e-3) / 1e12, 1)}
+        if args.full:
+            out["eager_ms_per_pair"] = round(res["eager"], 3)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
@@ -679,7 +747,7 @@ def preembed_main(args, dev, world, rank):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            m(input_ids=ids, attention_mask=mask)
+            hidden = m(input_ids=ids, attention_mask=mask)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -689,6 +757,7 @@ def preembed_main(args, dev, world, rank):
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = t.item()
+    dump_outputs(args.dump_outputs, rank, embeddings=hidden)
     if rank == 0:
         D, I, S = 384, 1536, 256
         flops = 12 * (3 * L * D * D + L * D * D + 2 * L * D * I + 2 * L * L * D + 2 * L * 2 * S * D) * 2
@@ -732,7 +801,7 @@ def preembed_image_main(args, dev, world, rank):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            m(px)
+            hidden = m(px)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -742,6 +811,7 @@ def preembed_image_main(args, dev, world, rank):
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = t.item()
+    dump_outputs(args.dump_outputs, rank, embeddings=hidden)
     if rank == 0:
         R0 = cfg.image_size // cfg.patch_size
         flops = 2 * R0 * R0 * 3 * cfg.patch_size ** 2 * cfg.embed_dim
@@ -780,11 +850,17 @@ def main():
     ap.add_argument("--precision", choices=["bf16", "fp32"], default=None,
                     help="train: fp32 (default; the reference's arithmetic, bf16 reported beside it); other workloads: bf16")
     ap.add_argument("--mode", choices=["finetune", "frozen"], default="finetune")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: GEMM probe steps + roofline, the bf16 leg, CPU baselines, the "
+                         "comparisons with the oracle, the workloads' secondary figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, <= 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--workload", choices=["train", "forward", "extract", "retrieve", "preprocess", "latency",
                                                   "preembed", "preembed_image"],
                     default="train")
-    ap.add_argument("--no-bf16", action="store_true", help="skip the secondary bf16 leg of the fp32 headline")
+    ap.add_argument("--no-bf16", action="store_true",
+                    help="with --full: skip the secondary bf16 leg of the fp32 headline")
     ap.add_argument("--no-graph", action="store_true",
                     help="time eager steps instead of HIP-graph replays of the captured step (N = 1)")
     args = ap.parse_args()
@@ -823,10 +899,10 @@ def main():
         if args.batch == 256:
             args.batch = 64
         return preembed_main(args, dev, world, rank)
-    res = train_leg(args, dev, world, rank, args.precision)
+    res = train_leg(args, dev, world, rank, args.precision, dump=True)
     log(f"{args.precision} leg: {res['pairs']:.1f} pairs/s")
     sec = None
-    if args.precision == "fp32" and not args.no_bf16:
+    if args.full and args.precision == "fp32" and not args.no_bf16:
         torch.cuda.empty_cache()
         sec = train_leg(args, dev, world, rank, "bf16")
         log(f"bf16 leg: {sec['pairs']:.1f} pairs/s")
@@ -839,14 +915,13 @@ def main():
                        "bert-base-uncased + ViT-B/16 + fusion head (768/768, E=256, H=8), fwd+bwd+AdamW",
                        "global_batch": args.batch * world, "seq_len": 128, "image_size": 224,
                        "parallelism": f"dp{world}"},
-            "roofline": res["roofline"], "step_launch": res["launch"],
+            "step_launch": res["launch"],
             "step_tflops_per_gpu": round(res["step_tflops"], 1),
             "roofline_step_frac": round(res["step_tflops"] / res["step_peak"][0], 4),
             "roofline_step_peak": {"peak": round(res["step_peak"][0], 1), "unit": "TFLOP/s", "note":
                                    res["step_peak"][1] + f"; step FLOPs = {GFLOP_PER_PAIR[args.mode]} GFLOP/pair "
                                    "(SURVEY 8(d), algorithmic)"},
-            "gemm_ms_per_step": res["gemm_ms"], "gemm_tflops_all_shapes": res["gemm_tf"],
-            "gemm_kernels": res["gemm_kinds"], "final_loss": res["loss"], "first_step_loss": res["first_loss"],
+            "final_loss": res["loss"], "first_step_loss": res["first_loss"],
             "dp_check": res["dp_check"],
             "peak_memory_gb": res["peak_memory_gb"], "memory": res["memory"],
             "fp32_gemm": ("split operands: x = hi + mid + lo bf16 planes staged together per 32-deep K-step, the six "
@@ -855,18 +930,21 @@ def main():
                           "MMFD_FP32_GEMM=native selects the fp32 MFMA)" if K.fp32_gemm_mode() == 1
                           else "fp32 MFMA (v_mfma_f32_16x16x4f32)"),
         }
+        if args.full:
+            out.update({"roofline": res["roofline"], "gemm_ms_per_step": res["gemm_ms"],
+                        "gemm_tflops_all_shapes": res["gemm_tf"], "gemm_kernels": res["gemm_kinds"]})
         if sec is not None:
             out["bf16"] = {"value": round(sec["pairs"], 2), "unit": "pairs/s", "ms_per_step": round(sec["ms"], 3),
                            "step_tflops_per_gpu": round(sec["step_tflops"], 1),
                            "roofline_step_frac": round(sec["step_tflops"] / sec["step_peak"][0], 4),
                            "roofline": sec["roofline"], "final_loss": sec["loss"],
                            "note": "secondary: bf16 MFMA operands, fp32 accumulation / master weights / optimizer"}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"], out["parity"] = cpu_baseline(dev)
             except Exception as e:  # the baseline must never hide the GPU number
                 out["cpu_baseline"] = {"error": repr(e)}
-        fx = first_step_parity(args, res)
+        fx = first_step_parity(args, res) if args.full else None
         if fx is not None:
             out.setdefault("parity", {})["first_step_vs_oracle"] = fx
         print(json.dumps(out), flush=True)
@@ -874,8 +952,10 @@ def main():
         dist.destroy_process_group()
 
 
-def train_leg(args, dev, world, rank, precision):
-    """`--warmup` untimed + `--steps` timed training steps of one precision; returns the numbers."""
+def train_leg(args, dev, world, rank, precision, dump=False):
+    """`--warmup` untimed + `--steps` timed training steps of one precision, then (`--full`) the
+    GEMM probe steps; returns the numbers. `dump`: this leg's last timed step is what
+    `--dump-outputs` writes."""
     from mmfd import kernels as K
     from mmfd.dataset import synthetic_batch
     from mmfd.train import build_flagship
@@ -954,6 +1034,23 @@ def train_leg(args, dev, world, rank, precision):
     pairs = args.batch * world * args.steps / elapsed
     loss_val = loss[0].item()
     log(f"{precision} timed: {pairs:.1f} pairs/s, {ms:.1f} ms/step")
+    if dump and args.dump_outputs:
+        # what the last timed step gave its caller: the loss vector [total, tt, ti, it, ii], and the
+        # parameters it updated in place (all trained tensors flattened in order; sampled)
+        dump_outputs(args.dump_outputs, rank, loss=loss,
+                     parameters=torch.cat([p.detach().reshape(-1).float() for p in tr.params]))
+    res = {"pairs": pairs, "ms": ms, "loss": round(loss_val, 4), "loss_exact": loss_val,
+           "first_loss": None if first_loss is None else [round(v, 6) for v in first_loss.double().cpu().tolist()],
+           "dp_check": dp_check,
+           "launch": (("one HIP graph per step (captured fwd + bwd + AdamW" + (" + RCCL gradient all-reduce)" if world > 1
+                       else ")") if graphed else "eager kernel launches")
+                      + ("; text / image encoders on two streams" if tr.concurrent else "")),
+           "step_tflops": pairs / world * GFLOP_PER_PAIR[args.mode] / 1e3,
+           "step_peak": step_peak(precision), "peak_memory_gb": round(peak_gb, 1), "memory": mem,
+           "opt_steps": opt_steps, "world": world}
+    if not args.full:
+        del tr, batch
+        return res
 
     # per-GEMM device times from two more eager steps of the same trainer after the timed region
     # (events cannot be timed inside a graph), with the two encoders on ONE stream: in the timed
@@ -992,7 +1089,6 @@ def train_leg(args, dev, world, rank, precision):
     kinds = {k: {"launches_per_step": v["launches"] // steps_in_prof, "avg_us": round(1000.0 * v["ms"] / v["launches"], 1),
                  "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 1)}
              for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])}
-    tr_conc = conc
     del tr, batch
     roof = {"bound": "mfma", "kernel": dom_name, "achieved": round(achieved, 1), "peak": round(peak, 1),
             "unit": "TFLOP/s", "frac": round(achieved / peak, 4), "traffic": traffic,
@@ -1013,16 +1109,8 @@ def train_leg(args, dev, world, rank, precision):
     # its wave among MFMAs (V2 / V8 / V9: ~45 cycles, not contention between waves, V5-V7)
     roof["mfma_only_rate_note"] = ("bf16 MFMA-only loop on random operands: 0.71-0.81 of the dense peak "
                                    "(power-limited clock; profiles/r06_g4loop_mb_dma_forms.log V0)")
-    return {"pairs": pairs, "ms": ms, "loss": round(loss_val, 4), "loss_exact": loss_val, "gemm_ms": round(gemm_ms, 2), "gemm_kinds": kinds,
-            "first_loss": None if first_loss is None else [round(v, 6) for v in first_loss.double().cpu().tolist()],
-            "dp_check": dp_check,
-            "launch": (("one HIP graph per step (captured fwd + bwd + AdamW" + (" + RCCL gradient all-reduce)" if world > 1
-                        else ")") if graphed else "eager kernel launches")
-                       + ("; text / image encoders on two streams" if tr_conc else "")
-                       + "; GEMM times from 2 eager probe steps after the timed region, encoders serialized"),
-            "gemm_tf": round(gemm_tf, 1), "step_tflops": pairs / world * GFLOP_PER_PAIR[args.mode] / 1e3,
-            "step_peak": step_peak(precision), "roofline": roof, "peak_memory_gb": round(peak_gb, 1), "memory": mem,
-            "opt_steps": opt_steps, "world": world}
+    return {**res, "gemm_ms": round(gemm_ms, 2), "gemm_kinds": kinds, "gemm_tf": round(gemm_tf, 1), "roofline": roof,
+            "launch": res["launch"] + "; GEMM times from 2 eager probe steps after the timed region, encoders serialized"}
 
 
 def first_step_parity(args, res):

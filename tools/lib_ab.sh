@@ -14,7 +14,7 @@ for r in 1 2; do
     for w in ${AB_WHAT:-gemm bench}; do
       case $w in
         gemm) timeout -k 10 300 python3 tools/gemm_bench.py --dtype $DT --iters 10 > $O/gemm_${v}_$r.log 2>&1 ;;
-        bench) timeout -k 10 300 python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --precision $DT --no-bf16 > $O/bench_${v}_$r.log 2>&1 ;;
+        bench) timeout -k 10 300 python3 bench.py --steps 8 --warmup 2 --full --no-cpu-baseline --precision $DT --no-bf16 > $O/bench_${v}_$r.log 2>&1 ;;
         attn) timeout -k 10 200 python3 tools/attn_bench.py --dtype $DT --iters 20 > $O/attn_${v}_$r.log 2>&1 ;;
       esac
     done

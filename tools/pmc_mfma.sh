@@ -12,4 +12,4 @@ OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 timeout -s KILL 300 rocprofv3 --pmc SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_VALU_MFMA_BUSY_CYCLES \
   SQ_INSTS_MFMA SQ_INSTS_VALU SQ_WAIT_ANY SQ_WAVE_CYCLES GRBM_GUI_ACTIVE -d $OUT/mfma -o run --output-format csv -- \
-  python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline $BENCH_ARGS > $OUT/bench_mfma.json
+  python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline $BENCH_ARGS > $OUT/bench_mfma.json

@@ -39,7 +39,7 @@ def main(src, tag):
     prof = os.path.join(ROOT, "profiles")
     with open(os.path.join(prof, f"{tag}_mfma.json"), "w") as f:
         json.dump({"tag": tag, "source": "rocprofv3 --pmc (one pass) over python3 bench.py --steps 2 --warmup 1 "
-                   "--no-cpu-baseline " + os.environ.get("BENCH_ARGS", ""), "kernels": out}, f, indent=1)
+                   "--full --no-cpu-baseline " + os.environ.get("BENCH_ARGS", ""), "kernels": out}, f, indent=1)
     top = sorted(out.items(), key=lambda kv: -kv[1]["mfma_flops_per_dispatch"] * kv[1]["dispatches"])[:8]
     for k, v in top:
         print(f"{k}: util {v['mfma_util']:.3f} valu/mfma {v['valu_per_mfma']:.2f} wait {v['wait_any_frac']:.2f}")

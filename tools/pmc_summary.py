@@ -110,7 +110,7 @@ def main(src, tag):
         out[k] = {"dispatches": max(nf, nw), "fetch_bytes_per_dispatch": fb, "write_bytes_per_dispatch": wb,
                   "traffic_bytes_per_dispatch": fb + wb, "avg_ns_kernel_trace": avg_ns.get(k)}
     meta = {"tag": tag, "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over "
-            "python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline; FETCH_SIZE doubled per the gfx950 "
+            "python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline; FETCH_SIZE doubled per the gfx950 "
             "correction", "kernels": out}
     with open(os.path.join(prof, f"{tag}_hbm_traffic.json"), "w") as f:
         json.dump(meta, f, indent=1)

@@ -1,1 +1,7 @@
-cd $GRAFT_REPO_ROOT && export TMPDIR=/tmp && mkdir -p gpurun_out/prof_ext && timeout -k 10 500 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_ext/trace -o run --output-format csv -- python3 bench.py --workload extract --steps 3 --warmup 1 --no-cpu-baseline > gpurun_out/prof_ext/bench.json 2> gpurun_out/prof_ext/bench.err
+#!/bin/bash
+# kernel trace of the evidence-corpus workload (both precisions and the GEMM probe step: --full)
+cd "$(dirname "$0")/.." || exit 1
+OUT=${OUT:-out}/prof_ext
+mkdir -p $OUT
+timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- \
+  python3 bench.py --workload extract --steps 3 --warmup 1 --full --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err
