@@ -198,7 +198,15 @@ typedef struct mmfd_attn_args {
   void* dk; int64_t dk_sb, dk_st;
   void* dv; int64_t dv_sb, dv_st;
   float* delta;                    /* workspace [B][H][Lq] fp32 */
-  float* d_rel_bias;               /* must be NULL (the relative bias is inference-only, MPNet) */
+  float* d_rel_bias;               /* NULL, or the gradient with respect to rel_bias: fp32 [B][H][Lq][Lk],
+                                      contiguous, 16-B aligned, dS = P * (dP - delta) with P = exp(S - lse),
+                                      dP = dO V^T, delta = rowsum(dO * O) — `scale` is not applied (the bias
+                                      enters S unscaled). Needs a per-batch rel_bias (rel_bias_sb = H*Lq*Lk,
+                                      rel_bias_mod = 0; DeBERTa c2p + p2c), dropout_p = 0, no cosine
+                                      attention, B*H <= 65535, and must not alias rel_bias. Columns of keys
+                                      masked by key_bias (-FLT_MAX, mmfd_mask_to_bias) are exactly 0 in rows
+                                      that have a real key. dq / dk / dv are what the same call without
+                                      d_rel_bias writes (a separate kernel after them). */
   int accumulate_dq;               /* 1: dq += result (else overwrite) */
   int accumulate_dkv;              /* 1: dk += ..., dv += ... */
   int64_t rel_bias_sb;             /* batch stride of rel_bias in floats (0 = shared by the batch) */
@@ -327,6 +335,18 @@ int mmfd_rel_bias(int64_t H, int64_t Lq, int64_t Lk, const int32_t* bucket, cons
 int mmfd_deberta_rel_bias(int dtype, int64_t B, int64_t H, int64_t L, const void* c2p, const void* p2c, int64_t ld,
                           const int32_t* c2p_idx, const int32_t* p2c_idx, float inv_scale, float* out,
                           mmfd_stream_t stream);
+/* The adjoint of mmfd_deberta_rel_bias (DeBERTa fine-tuning): from ds = d(loss)/d(out), fp32 [B][H][L][L]
+   (mmfd_attn_args.d_rel_bias),
+     dc2p[h][b*L+i][s] = inv_scale * sum_{j : c2p_idx[i][j] == s} ds[b][h][i][j]
+     dp2c[h][b*L+j][s] = inv_scale * sum_{i : p2c_idx[j][i] == s} ds[b][h][i][j]
+   in the forward's layout ([H][B*L][ld], dtype fp32 or bf16, fp32 accumulation, one output rounding).
+   Every column s < ld is written (0 where no index maps to it); indices must be < ld. Deterministic and
+   free of atomics: c2p_idx[i][.] and p2c_idx[j][.] must be monotone along their second index (true of the
+   log-bucket indices; mmfd.kernels checks it on the host), so each element is the sum of one contiguous
+   run, taken in ascending order by a single thread. 16 output rows live in LDS: ld <= 959. */
+int mmfd_deberta_rel_bias_bwd(int dtype, int64_t B, int64_t H, int64_t L, const float* ds, const int32_t* c2p_idx,
+                              const int32_t* p2c_idx, float inv_scale, void* dc2p, void* dp2c, int64_t ld,
+                              mmfd_stream_t stream);
 /* x[r][:] = 0 where mask[r] == 0 (DebertaV2Embeddings: embeddings * mask, :552-559), x [rows][ldx] */
 int mmfd_mask_rows(int dtype, int64_t rows, int64_t D, void* x, int64_t ldx, const int64_t* mask,
                    mmfd_stream_t stream);
@@ -336,6 +356,16 @@ int mmfd_mask_rows(int dtype, int64_t rows, int64_t D, void* x, int64_t ldx, con
 int mmfd_attn_fill_masked_rows(int dtype, int64_t B, int64_t H, int64_t L, int64_t Dh, const void* v, int64_t v_sb,
                                int64_t v_st, void* o, int64_t o_sb, int64_t o_st, const int64_t* mask,
                                mmfd_stream_t stream);
+/* The adjoint of mmfd_attn_fill_masked_rows, in two phases around mmfd_attn_bwd (q-layout views as there;
+   gsum: fp32 [B][H*Dh] workspace carried from phase 0 to phase 1):
+     phase 0 (before mmfd_attn_bwd; dv unused): gsum[b][h][:] = (1/L) * sum_{i : mask[b][i] == 0} dout[b][i][h][:]
+       and those rows of dout are set to 0 in place, so the attention backward sees no gradient for them;
+     phase 1 (after mmfd_attn_bwd; dout and mask unused): dv[b][j][h][:] += gsum[b][h][:] for every key j,
+       padded keys included (the forward averaged v over all L keys).
+   Sums in fp32 in a fixed order (deterministic). */
+int mmfd_attn_fill_masked_rows_bwd(int dtype, int phase, int64_t B, int64_t H, int64_t L, int64_t Dh, void* dout,
+                                   int64_t do_sb, int64_t do_st, void* dv, int64_t dv_sb, int64_t dv_st,
+                                   const int64_t* mask, float* gsum, mmfd_stream_t stream);
 /* scatter-add the gradient of the pre-LN sum into the three tables (modeling_bert.py BertEmbeddings:
    word[id] += row, pos[t] += row, type[tt] += row), deterministically: the word rows are stably
    radix-sorted by id and each id's rows summed in row order by one writer; the type table reduces

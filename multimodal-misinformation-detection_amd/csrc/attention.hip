@@ -13,7 +13,9 @@
 //   backward : two kernels, no atomics (deterministic): dK/dV per 64-key block looping over query
 //              blocks (S = Q K^T puts the key on the lane: P and dS are directly the A operands of
 //              dV = P^T dO and dK = dS^T Q), and dQ per 64-query block looping over key blocks
-//              (S^T again). delta = rowsum(dO * O) comes from a small kernel first.
+//              (S^T again). delta = rowsum(dO * O) comes from a small kernel first. The gradient of
+//              a per-batch additive bias (mmfd_attn_args.d_rel_bias, DeBERTa) is a third kernel of the
+//              dQ shape that writes dS itself (attn_bwd_ds_kernel).
 // Dropout on P (layers.py:53 / SDPA dropout_p) is counter based: index ((b*H+h)*Lq+q)*Lk+k.
 #include "common.h"
 #include <algorithm>
@@ -632,6 +634,91 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(AttnP p) {
         float vq = dq[d][r] * p.scale;
         if (p.acc_dq) vq += to_f32(*pq);
         *pq = from_f32<T>(vq);
+      }
+    }
+  }
+}
+
+// --------------------------------------------------------------------------------------------
+// backward: dS, the gradient of a per-batch additive rel_bias [B][H][Lq][Lk] (DeBERTa c2p + p2c)
+// --------------------------------------------------------------------------------------------
+// Workgroup = 64 queries, wave = 16 queries, looping over 64-key blocks staged in LDS exactly like
+// attn_bwd_dq_kernel: S^T = K Q^T and dP^T = V dO^T on MFMAs put the query on the lane, so lse and
+// delta are lane-local, and a lane holds 4 consecutive keys of its query:
+//   dS[q][k] = P (dP - delta),  P = exp(scale q.k + key_bias[k] + rel_bias[q][k] - lse[q])
+// (no `scale`: the bias enters S unscaled; no dropout: mmfd_attn_bwd refuses the combination).
+// It runs after the dQ / dK/dV kernels of the same call and reads the delta they left; those
+// kernels are untouched. Stores are 16-B vector stores when Lk % 4 == 0, else 4-B ones.
+//
+// Masked keys come out exactly 0: key_bias of a masked key is -FLT_MAX (mmfd_mask_to_bias), which
+// absorbs the finite rest of the score, while lse of a row with at least one real key is finite, so
+// the exponent is far below DS_EXP_MIN = -104 < ln(2^-150): there exp() rounds to +0 in fp32
+// whatever the rounding of the intrinsic, and the kernel returns the literal 0 for such arguments
+// instead of calling it. 0 * (dP - delta) is 0 because dP and delta are finite for finite inputs.
+// (A row whose keys are ALL masked has lse near -FLT_MAX and uniform P, as in the forward; DeBERTa
+// zeroes dO of those rows first, mmfd_attn_fill_masked_rows_bwd, which makes their dS 0 as well.)
+constexpr float DS_EXP_MIN = -104.f;
+
+template <typename T, int D>
+__global__ void __launch_bounds__(256) attn_bwd_ds_kernel(AttnP p, float* __restrict__ ds_out) {
+  using C = AT<T, D>;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* k_row = smem;
+  char* v_row = smem + C::TILE;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
+  const int64_t bh = blockIdx.y, b = bh / p.H, h = bh % p.H;
+  const int64_t q0 = (int64_t)blockIdx.x * 64 + wave * 16;
+  const int64_t myq = q0 + li;
+  const T* qb = reinterpret_cast<const T*>(p.q) + b * p.q_sb + h * p.D;
+  const T* kb = reinterpret_cast<const T*>(p.k) + b * p.k_sb + h * p.D;
+  const T* vb = reinterpret_cast<const T*>(p.v) + b * p.v_sb + h * p.D;
+  const T* dob = reinterpret_cast<const T*>(p.dout) + b * p.do_sb + h * p.D;
+
+  uint4 qf[C::KCH], dof[C::KCH];
+  load_row_regs<T, D>(qf, qb, p.q_st, myq, p.Lq, lane, p.D);
+  load_row_regs<T, D>(dof, dob, p.do_st, myq, p.Lq, lane, p.D);
+  const bool qok = myq < p.Lq;
+  const float lse = qok ? p.lse[bh * p.Lq + myq] : INFINITY;
+  const float dlt = qok ? p.delta[bh * p.Lq + myq] : 0.f;
+  const int64_t rowoff = (bh * p.Lq + (qok ? myq : 0)) * p.Lk;  // [B][H][Lq][Lk] contiguous, as rel_bias
+  const float* relrow = p.rel_bias + rowoff;
+  float* dsrow = ds_out + rowoff;
+  const bool vec4 = (p.Lk & 3) == 0;  // rows then start 16-B aligned (base alignment checked by the host)
+
+  for (int64_t k0 = 0; k0 < p.Lk; k0 += 64) {
+    __syncthreads();
+    stage_rows<T, D, false>(k_row, kb, p.k_st, k0, p.Lk, tid, p.D);
+    stage_rows<T, D, false>(v_row, vb, p.v_st, k0, p.Lk, tid, p.D);
+    __syncthreads();
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      f32x4 sv = f32x4{0.f, 0.f, 0.f, 0.f}, dp = sv;
+#pragma unroll
+      for (int kc = 0; kc < C::KCH; ++kc) {
+        Mma<T>::run(sv, row_frag<T, D>(k_row, ks, kc, lane), qf[kc]);
+        Mma<T>::run(dp, row_frag<T, D>(v_row, ks, kc, lane), dof[kc]);
+      }
+      const int64_t key0 = k0 + ks * 16 + 4 * g;
+      if (!qok || key0 >= p.Lk) continue;
+      float ds[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int64_t key = key0 + r;
+        ds[r] = 0.f;
+        if (key < p.Lk) {
+          float sc = sv[r] * p.scale + relrow[key];
+          if (p.key_bias) sc += p.key_bias[b * p.Lk + key];
+          const float x = sc - lse;
+          const float pr = x < DS_EXP_MIN ? 0.f : __expf(x);
+          ds[r] = pr * (dp[r] - dlt);
+        }
+      }
+      if (vec4) {
+        *reinterpret_cast<float4*>(dsrow + key0) = make_float4(ds[0], ds[1], ds[2], ds[3]);
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (key0 + r < p.Lk) dsrow[key0 + r] = ds[r];
       }
     }
   }
@@ -2367,7 +2454,14 @@ int fill(const mmfd_attn_args& a, AttnP& p, bool bwd) {
   if (bwd) {
     MMFD_CHECK_ARG(a.dout && a.dq && a.dk && a.dv && a.delta, "attn_bwd: null pointer");
     MMFD_CHECK_ARG(al(a.dout, a.do_sb, a.do_st), "attn_bwd: dout alignment");
-    MMFD_CHECK_ARG(a.d_rel_bias == nullptr, "attn_bwd: relative-bias gradient not supported");
+    if (a.d_rel_bias) {  // the gradient of a per-batch bias (attn_bwd_ds_kernel)
+      MMFD_CHECK_ARG(a.rel_bias && a.rel_bias_sb == a.H * a.Lq * a.Lk && a.rel_bias_mod == 0,
+                     "attn_bwd: d_rel_bias needs a per-batch rel_bias [B][H][Lq][Lk] (rel_bias_sb = H*Lq*Lk, rel_bias_mod = 0)");
+      MMFD_CHECK_ARG(a.dropout_p <= 0.f, "attn_bwd: d_rel_bias with attention dropout is not supported");
+      MMFD_CHECK_ARG((const float*)a.d_rel_bias != a.rel_bias, "attn_bwd: d_rel_bias must not alias rel_bias");
+      MMFD_CHECK_ARG(((uintptr_t)a.d_rel_bias & 15) == 0, "attn_bwd: d_rel_bias must be 16-B aligned");
+      MMFD_CHECK_ARG(a.B * a.H <= 65535, "attn_bwd: d_rel_bias needs B*H <= 65535");
+    }
     MMFD_CHECK_ARG(a.cos_logit_scale == nullptr, "attn_bwd: cosine attention is inference-only");
   }
   p.B = a.B; p.H = a.H; p.Lq = a.Lq; p.Lk = a.Lk; p.scale = a.scale; p.D = (int)a.D;
@@ -2506,6 +2600,13 @@ void launch_bwd_v2(const AttnP& p, hipStream_t s) {
 }
 
 template <typename T, int D>
+void launch_bwd_ds(const AttnP& p, float* ds, hipStream_t s) {
+  dim3 grid((unsigned)((p.Lq + 63) / 64), (unsigned)(p.B * p.H));
+  constexpr int lds = 2 * AT<T, D>::TILE;
+  hipLaunchKernelGGL((attn_bwd_ds_kernel<T, D>), grid, dim3(256), lds, s, p, ds);
+}
+
+template <typename T, int D>
 void launch_fwd(const AttnP& p, hipStream_t s) {
   dim3 grid((unsigned)((p.Lq + 63) / 64), (unsigned)(p.B * p.H));
   constexpr int lds = 2 * AT<T, D>::TILE;
@@ -2595,6 +2696,11 @@ extern "C" int mmfd_attn_bwd(const mmfd_attn_args* a, mmfd_stream_t stream) {
   else if (a->dtype == MMFD_BF16) { if (a->D > 32) launch_bwd<bf16, 64>(p, s); else launch_bwd<bf16, 32>(p, s); }
   else { if (a->D > 32) launch_bwd<float, 64>(p, s); else launch_bwd<float, 32>(p, s); }
   MMFD_CHECK_LAUNCH("attn_bwd");
+  if (a->d_rel_bias) {  // after the kernels above: it reads the delta they wrote
+    if (a->dtype == MMFD_BF16) { if (a->D > 32) launch_bwd_ds<bf16, 64>(p, a->d_rel_bias, s); else launch_bwd_ds<bf16, 32>(p, a->d_rel_bias, s); }
+    else { if (a->D > 32) launch_bwd_ds<float, 64>(p, a->d_rel_bias, s); else launch_bwd_ds<float, 32>(p, a->d_rel_bias, s); }
+    MMFD_CHECK_LAUNCH("attn_bwd d_rel_bias");
+  }
   if (a->dqkv_planes && !v2)  // the v1 kernels write fp32 only: split afterwards
     return mmfd_split3(p.B * p.Lq, W, (const float*)a->dq, W, a->dqkv_planes, stream);
   return 0;

@@ -196,11 +196,18 @@ void attn_bwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, con
               const std::optional<at::Tensor>& key_bias, const std::optional<at::Tensor>& rel_bias, int64_t rel_bias_sb,
               int64_t rel_bias_mod, double dropout_p, const std::optional<at::Tensor>& seed, int64_t salt,
               bool accumulate_dq, bool accumulate_dkv, const std::optional<at::Tensor>& dqkv_planes = std::nullopt,
-              bool planes_only = false, const std::optional<at::Tensor>& drop_mask = std::nullopt) {
+              bool planes_only = false, const std::optional<at::Tensor>& drop_mask = std::nullopt,
+              const std::optional<at::Tensor>& d_rel_bias = std::nullopt) {
   mmfd_attn_args a = attn_args(q, k, v, heads, scale, key_bias, rel_bias, rel_bias_sb, rel_bias_mod, dropout_p, seed, salt);
   const void* p;
   head_view(o, "o", &p, &a.o_sb, &a.o_st); a.o = const_cast<void*>(p);
   a.lse = const_cast<float*>(lse.data_ptr<float>());
+  if (d_rel_bias.has_value() && d_rel_bias->defined()) {
+    TORCH_CHECK(d_rel_bias->scalar_type() == at::kFloat && d_rel_bias->is_contiguous() && d_rel_bias->is_cuda() &&
+                    d_rel_bias->numel() == a.B * a.H * a.Lq * a.Lk,
+                "mmfd::attn_bwd: d_rel_bias must be a contiguous fp32 device tensor [B, H, Lq, Lk]");
+    a.d_rel_bias = d_rel_bias->data_ptr<float>();
+  }
   head_view(dout, "dout", &p, &a.do_sb, &a.do_st); a.dout = p;
   head_view(dq, "dq", &p, &a.dq_sb, &a.dq_st); a.dq = const_cast<void*>(p);
   head_view(dk, "dk", &p, &a.dk_sb, &a.dk_st); a.dk = const_cast<void*>(p);
@@ -344,7 +351,8 @@ TORCH_LIBRARY(mmfd, m) {
   m.def("attn_bwd(Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor dout, Tensor(a!) dq, Tensor(b!) dk, "
         "Tensor(c!) dv, int heads, float scale, Tensor? key_bias, Tensor? rel_bias, int rel_bias_sb, int rel_bias_mod, "
         "float dropout_p, Tensor? seed, int salt, bool accumulate_dq, bool accumulate_dkv, "
-        "Tensor(d!)? dqkv_planes=None, bool planes_only=False, Tensor? drop_mask=None)-> ()");
+        "Tensor(d!)? dqkv_planes=None, bool planes_only=False, Tensor? drop_mask=None, "
+        "Tensor(e!)? d_rel_bias=None) -> ()");
   m.def("layernorm_fwd(Tensor x, Tensor gamma, Tensor beta, float eps, Tensor(a!) y, Tensor(b!) mean, "
         "Tensor(c!) rstd, Tensor(d!)? planes=None) -> ()");
   m.def("layernorm_bwd(Tensor dy, Tensor x, Tensor gamma, Tensor mean, Tensor rstd, Tensor(a!) dx, Tensor? dx_add, "

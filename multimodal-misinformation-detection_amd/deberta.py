@@ -18,8 +18,16 @@ MI355X mapping: QKV is one packed GEMM; the position projections of all heads ar
 512 relative embeddings against the same packed weight; c2p / p2c are per-head MFMA GEMMs
 ([B*L, d] x [d, 512]); one gather kernel turns them into the [B, H, L, L] fp32 additive bias the
 flash-attention kernels consume (batch-strided rel_bias); padded-row fix-ups are two tiny kernels.
-Inference only (the reference freezes its encoders, train.py:335-340, and the pre-embedding
-pass runs under no_grad): a forward that would need gradients raises.
+
+By default inference only (the reference freezes its encoders, train.py:335-340, and the
+pre-embedding pass runs under no_grad): a forward that would need gradients raises. With
+`DebertaV2Config(trainable=True)` a forward under grad runs as ONE autograd node (`_DebertaFn`, shaped
+like encoders._BertFn) whose backward is `deberta_backward`: the post-LN block backward of BERT, and
+through the disentangled bias the attention backward's dS (mmfd_attn_args.d_rel_bias), its scatter
+back to dc2p / dp2c (mmfd_deberta_rel_bias_bwd), four per-head GEMMs into dQ, dK and the position
+projections' gradients, and the padded-row fix-up's adjoint (mmfd_attn_fill_masked_rows_bwd). Each
+layer keeps its [B, H, L, L] fp32 bias for the backward (DESIGN f1). Dropout is not implemented on
+this path (HF's default is 0.1): the config's dropout probabilities must be 0 when training.
 """
 from __future__ import annotations
 
@@ -49,6 +57,10 @@ class DebertaV2Config:
     max_relative_positions: int = -1
     layer_norm_eps: float = 1e-7
     pad_token_id: int = 0
+    # fine-tuning (opt-in): with trainable=False the model is inference-only exactly as before
+    trainable: bool = False
+    hidden_dropout_prob: float = 0.0            # (HF default 0.1; only 0 is implemented for training)
+    attention_probs_dropout_prob: float = 0.0
 
 
 def log_bucket_relative_positions(L: int, bucket_size: int, max_position: int) -> np.ndarray:
@@ -77,6 +89,9 @@ def _bias_indices(L, S, max_position, device):
         c2p = np.clip(rel + S, 0, 2 * S - 1).astype(np.int32)
         p2c = np.clip(-rel + S, 0, 2 * S - 1).astype(np.int32)
         t = _IDX[key] = (torch.from_numpy(c2p).to(device), torch.from_numpy(p2c).to(device))
+        # the backward's run-sum kernel needs monotone index rows: checked here once per cached pair,
+        # on the host copies (raises otherwise), so a captured training step finds the pair verified
+        K.verify_rel_indices(*t, host=(c2p, p2c))
     return t
 
 
@@ -145,18 +160,32 @@ class DebertaV2Model(Bk.CachedWeights, nn.Module):
         first = next(iter(params.values()))
         if not first.is_cuda:
             raise RuntimeError("mmfd DebertaV2Model runs on the HIP device: call .to('cuda') first")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params.values()):
+        c = self.config
+        keep = torch.is_grad_enabled() and any(p.requires_grad for p in params.values())
+        if keep and not c.trainable:
             raise NotImplementedError("mmfd DebertaV2Model is inference-only (frozen encoder, train.py:335-340): "
-                                      "call it under torch.no_grad() or freeze its parameters")
+                                      "call it under torch.no_grad() or freeze its parameters, or build it with "
+                                      "DebertaV2Config(trainable=True)")
+        if c.trainable and self.training and (c.hidden_dropout_prob > 0 or c.attention_probs_dropout_prob > 0):
+            raise NotImplementedError("mmfd DebertaV2Model trains without dropout only: set hidden_dropout_prob and "
+                                      "attention_probs_dropout_prob to 0 (HF's default is 0.1)")
+        if keep:
+            out = _DebertaFn.apply(self, list(params.keys()), input_ids, attention_mask, *params.values())
+            return EncoderOutput(last_hidden_state=out)
         P = {n: p.detach() for n, p in params.items()}
         ctx = Bk.StepCtx(P, self.compute_dtype, shadows=Bk.shadow_store(self))
-        ctx.cache_derived = True          # frozen encoder: packed QKV biases persist across calls
+        # frozen encoder: packed QKV biases persist across calls (not for a trainable model: mmfd's
+        # AdamW moves its parameters without bumping their version counters, see StepCtx.derived)
+        ctx.cache_derived = not c.trainable
         out = deberta_forward(self, ctx, input_ids, attention_mask)
         return EncoderOutput(last_hidden_state=out)
 
 
-def deberta_forward(model: DebertaV2Model, ctx: Bk.StepCtx, input_ids, attention_mask):
+def deberta_forward(model: DebertaV2Model, ctx: Bk.StepCtx, input_ids, attention_mask, st=None):
+    """`st` (a dict, training): filled with what deberta_backward reads; the kernels and their order
+    are the same either way, so the outputs are too"""
     cfg = model.config
+    keep = st is not None
     dev = ctx.P["embeddings.word_embeddings.weight"].device
     ids = input_ids.to(dev).long().contiguous()
     B, L = ids.shape
@@ -170,14 +199,19 @@ def deberta_forward(model: DebertaV2Model, ctx: Bk.StepCtx, input_ids, attention
     zp = model._zero_pos.get((L, str(dev)))
     if zp is None:
         zp = model._zero_pos[(L, str(dev))] = torch.zeros(L, D, device=dev, dtype=torch.float32)
-    x = K.embed_ln_infer(ids, None, ctx.P["embeddings.word_embeddings.weight"], zp,
-                         ctx.P["embeddings.LayerNorm.weight"], ctx.P["embeddings.LayerNorm.bias"], eps, dt)
+    if keep:
+        s0, x, m0, r0 = K.embed_ln_train(ids, None, ctx.P["embeddings.word_embeddings.weight"], zp,
+                                         ctx.P["embeddings.LayerNorm.weight"], ctx.P["embeddings.LayerNorm.bias"],
+                                         eps, dt)
+    else:
+        x = K.embed_ln_infer(ids, None, ctx.P["embeddings.word_embeddings.weight"], zp,
+                             ctx.P["embeddings.LayerNorm.weight"], ctx.P["embeddings.LayerNorm.bias"], eps, dt)
     K.mask_rows(x, mask)
     key_bias = K.mask_to_bias(mask)
     c2p_idx, p2c_idx = _bias_indices(L, S, model.max_relative_positions, dev)
     rel = ctx.P["encoder.rel_embeddings.weight"][: 2 * S]
-    relE, _, _ = K.layernorm_fwd(K.cast(rel, dt) if dt != torch.float32 else rel.contiguous(),
-                                 ctx.P["encoder.LayerNorm.weight"], ctx.P["encoder.LayerNorm.bias"], eps)
+    rel_in = K.cast(rel, dt) if dt != torch.float32 else rel.contiguous()
+    relE, mr, rr = K.layernorm_fwd(rel_in, ctx.P["encoder.LayerNorm.weight"], ctx.P["encoder.LayerNorm.bias"], eps)
     scale = 1.0 / math.sqrt(d * 3)
     c2p = torch.empty((H, B * L, 2 * S), device=dev, dtype=dt)
     p2c = torch.empty((H, B * L, 2 * S), device=dev, dtype=dt)
@@ -193,12 +227,112 @@ def deberta_forward(model: DebertaV2Model, ctx: Bk.StepCtx, input_ids, attention
             K.gemm(kh, pqh, out=p2c[h])                      # p2c = K_h posQ_h^T
         rb = K.deberta_rel_bias(c2p, p2c, c2p_idx, p2c_idx, B, L, scale)
         q3 = qkv.view(B, L, 3 * D)
-        o, _ = K.attn_fwd(q3[..., :D], q3[..., D:2 * D], q3[..., 2 * D:], H, scale=scale, key_bias=key_bias,
-                          rel_bias=rb)
+        o, lse = K.attn_fwd(q3[..., :D], q3[..., D:2 * D], q3[..., 2 * D:], H, scale=scale, key_bias=key_bias,
+                            rel_bias=rb)
         K.attn_fill_masked_rows(q3[..., 2 * D:], o, H, mask)
         s1, _ = Bk.linear(ctx, Bk.as2d(o), p + ".attention.output.dense", residual=x)
-        h1, _, _ = Bk.layernorm(ctx, s1, p + ".attention.output.LayerNorm", eps)
-        f, _ = Bk.linear(ctx, h1, p + ".intermediate.dense", act=K.ACT_GELU)
+        h1, m1, r1 = Bk.layernorm(ctx, s1, p + ".attention.output.LayerNorm", eps)
+        f, pre = Bk.linear(ctx, h1, p + ".intermediate.dense", act=K.ACT_GELU, keep_aux=keep)
         s2, _ = Bk.linear(ctx, f, p + ".output.dense", residual=h1)
-        x, _, _ = Bk.layernorm(ctx, s2, p + ".output.LayerNorm", eps)
+        x_out, m2, r2 = Bk.layernorm(ctx, s2, p + ".output.LayerNorm", eps)
+        if keep:
+            st["layers"].append((x, qkv, pos, rb, o, lse, s1, m1, r1, h1, pre, f, s2, m2, r2))
+        x = x_out
+    if keep:
+        st.update(ids=ids, mask=mask, key_bias=key_bias, idx=(c2p_idx, p2c_idx), s0=s0, m0=m0, r0=r0, rel_in=rel_in,
+                  relE=relE, mr=mr, rr=rr, scale=scale, bufs=(c2p, p2c))
     return x.view(B, L, D)
+
+
+def deberta_backward(model: DebertaV2Model, ctx: Bk.StepCtx, dout, st):
+    """Gradients of every parameter into ctx.grads, layers in reverse. Per layer: the BERT block
+    backward (FFN, both LayerNorms, output projection), then through the attention
+        S = scale Q K^T + key_bias + inv (c2p[i, c2p_idx[i, j]] + p2c[j, p2c_idx[j, i]])
+    with c2p = Q_h posK_h^T, p2c = K_h posQ_h^T: attn_bwd also emits dS (no dropout), its scatter
+    gives dc2p / dp2c, and per head dQ_h += dc2p_h posK_h, dK_h += dp2c_h posQ_h, dposK_h =
+    dc2p_h^T Q_h, dposQ_h = dp2c_h^T K_h. The packed Q|K|V weights collect two gradients: the token
+    stream (dqkv, x) and the position stream (dpos = dposQ | dposK, LayerNorm(rel_embeddings)); the
+    relative embeddings collect dpos W over all layers (fp32 accumulator)."""
+    cfg = model.config
+    ids, mask = st["ids"], st["mask"]
+    B, L = ids.shape
+    D, H = cfg.hidden_size, cfg.num_attention_heads
+    d = D // H
+    S2 = 2 * model.att_span
+    dt, scale = ctx.dt, st["scale"]
+    c2p_idx, p2c_idx = st["idx"]
+    relE = st["relE"]
+    dev = dout.device
+    dx = Bk.as2d(dout).contiguous()
+    dsb = torch.empty((B, H, L, L), device=dev, dtype=torch.float32)  # dS of one layer at a time
+    dc2p, dp2c = st["bufs"]                     # the forward's c2p / p2c buffers, free by now
+    drelE = torch.empty((S2, D), device=dev, dtype=torch.float32)
+    for i in reversed(range(cfg.num_hidden_layers)):
+        p = f"encoder.layer.{i}"
+        x, qkv, pos, rb, o, lse, s1, m1, r1, h1, pre, f, s2, m2, r2 = st["layers"][i]
+        st["layers"][i] = None
+        ds2, _ = Bk.layernorm_bwd(ctx, dx, s2, p + ".output.LayerNorm", m2, r2)
+        ctx.lin_grads([p + ".output.dense"], ds2, f)
+        dpre = Bk.linear_dx(ctx, ds2, p + ".output.dense", act=K.ACT_GELU_BWD, aux=pre)
+        ctx.lin_grads([p + ".intermediate.dense"], dpre, h1)
+        dh1 = Bk.linear_dx(ctx, dpre, p + ".intermediate.dense", residual=ds2)
+        ds1, _ = Bk.layernorm_bwd(ctx, dh1, s1, p + ".attention.output.LayerNorm", m1, r1)
+        ctx.lin_grads([p + ".attention.output.dense"], ds1, Bk.as2d(o))
+        do = Bk.linear_dx(ctx, ds1, p + ".attention.output.dense").view(B, L, D)
+        # padded query rows: their dO goes to dV of every key (mean of V in the forward), not into the attention
+        gsum = K.attn_fill_masked_rows_bwd(do, H, mask)
+        dqkv = torch.empty_like(qkv)
+        q3, dq3 = qkv.view(B, L, 3 * D), dqkv.view(B, L, 3 * D)
+        K.attn_bwd(q3[..., :D], q3[..., D:2 * D], q3[..., 2 * D:], o, lse, do, H, scale=scale, key_bias=st["key_bias"],
+                   rel_bias=rb, dq=dq3[..., :D], dk=dq3[..., D:2 * D], dv=dq3[..., 2 * D:], d_rel_bias=dsb)
+        K.attn_fill_masked_rows_bwd(do, H, mask, dv=dq3[..., 2 * D:], gsum=gsum)
+        K.deberta_rel_bias_bwd(dsb, c2p_idx, p2c_idx, B, L, scale, S2, dt, dc2p=dc2p, dp2c=dp2c)
+        dpos = torch.empty((S2, 2 * D), device=dev, dtype=dt)  # dposQ | dposK (the V third of pos is unused)
+        for h in range(H):
+            hq, hk = slice(h * d, (h + 1) * d), slice(D + h * d, D + (h + 1) * d)
+            K.gemm(dc2p[h], pos[:, hk], trans_b=True, out=dqkv[:, hq], beta=1.0)   # dQ_h += dc2p_h posK_h
+            K.gemm(dp2c[h], pos[:, hq], trans_b=True, out=dqkv[:, hk], beta=1.0)   # dK_h += dp2c_h posQ_h
+            K.gemm(dc2p[h], qkv[:, hq], trans_a=True, trans_b=True, out=dpos[:, hk])  # dposK_h = dc2p_h^T Q_h
+            K.gemm(dp2c[h], qkv[:, hk], trans_a=True, trans_b=True, out=dpos[:, hq])  # dposQ_h = dp2c_h^T K_h
+        names = [p + ".attention.self.query_proj", p + ".attention.self.key_proj", p + ".attention.self.value_proj"]
+        ctx.lin_grads(names, dqkv, x)                   # token stream (one packed GEMM)
+        ctx.lin_grads(names[:2], dpos, relE)            # position stream: accumulates onto the Q and K blocks
+        Wp, _ = ctx.w_packed(names)
+        K.gemm(dpos, Wp[:2 * D], trans_b=True, out=drelE, beta=0.0 if i == cfg.num_hidden_layers - 1 else 1.0)
+        dx = Bk.linear_dx(ctx, dqkv, Wp, residual=ds1)  # dx_in = ds1 + dQKV [Wq;Wk;Wv]
+        ctx.flush_ready()
+    # relative embeddings: LayerNorm backward of the summed position gradient
+    drel, _ = Bk.layernorm_bwd(ctx, drelE if dt == torch.float32 else K.cast(drelE, dt), st["rel_in"],
+                               "encoder.LayerNorm", st["mr"], st["rr"])
+    grel = K.zeros(ctx.P["encoder.rel_embeddings.weight"].shape, device=dev)  # rows past 2S (none by default): 0
+    K.cast(drel, torch.float32, out=grel[:S2])
+    ctx.grads["encoder.rel_embeddings.weight"] = grel
+    # embeddings: x = LayerNorm(word[id]) * mask
+    K.mask_rows(dx, mask)
+    dsum, _ = Bk.layernorm_bwd(ctx, dx, st["s0"], "embeddings.LayerNorm", st["m0"], st["r0"])
+    dword = K.zeros(ctx.P["embeddings.word_embeddings.weight"].shape, device=dev)
+    K.embed_bwd(ids, None, dsum, dword, None, None, padding_idx=cfg.pad_token_id)
+    ctx.grads["embeddings.word_embeddings.weight"] = dword
+    ctx.flush_ready()
+
+
+class _DebertaFn(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, model, names, input_ids, attention_mask, *params):
+        P = {n: p.detach() for n, p in zip(names, params)}
+        sc = Bk.StepCtx(P, model.compute_dtype, 0.0, None, training=model.training, shadows=Bk.shadow_store(model))
+        sc.grad_ready = getattr(model, "_grad_ready", None)
+        st = {"layers": []}
+        out = deberta_forward(model, sc, input_ids, attention_mask, st=st)
+        fctx.sc, fctx.st, fctx.model, fctx.names = sc, st, model, names
+        return out
+
+    @staticmethod
+    def backward(fctx, dout):
+        sc = fctx.sc
+        sc.enable_side_stream(dout.device)
+        deberta_backward(fctx.model, sc, dout.to(sc.dt), fctx.st)
+        sc.join_side()
+        grads = [sc.grads.get(n) for n in fctx.names]
+        fctx.sc = fctx.st = None
+        return (None, None, None, None, *grads)

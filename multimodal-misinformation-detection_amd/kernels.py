@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import weakref
 import zlib
 
 import torch
@@ -173,8 +174,11 @@ SIGNATURES = {
     "mmfd_global_avgpool": (_I, [_I, _I64, _I64, _I64, _VP, _VP, _VP]),
     "mmfd_rel_bias": (_I, [_I64, _I64, _I64, _VP, _VP, _VP, _VP]),
     "mmfd_deberta_rel_bias": (_I, [_I, _I64, _I64, _I64, _VP, _VP, _I64, _VP, _VP, _F, _VP, _VP]),
+    "mmfd_deberta_rel_bias_bwd": (_I, [_I, _I64, _I64, _I64, _VP, _VP, _VP, _F, _VP, _VP, _I64, _VP]),
     "mmfd_mask_rows": (_I, [_I, _I64, _I64, _VP, _I64, _VP, _VP]),
     "mmfd_attn_fill_masked_rows": (_I, [_I, _I64, _I64, _I64, _I64, _VP, _I64, _I64, _VP, _I64, _I64, _VP, _VP]),
+    "mmfd_attn_fill_masked_rows_bwd": (_I, [_I, _I, _I64, _I64, _I64, _I64, _VP, _I64, _I64, _VP, _I64, _I64, _VP, _VP,
+                                            _VP]),
     "mmfd_patchify": (_I, [_I, _I64, _I64, _I64, _I64, _I64, _VP, _VP, _VP]),
     "mmfd_vit_tokens_fwd": (_I, [_I, _I64, _I64, _I64, _VP, _VP, _VP, _VP, _VP]),
     "mmfd_vit_tokens_bwd": (_I, [_I, _I64, _I64, _I64, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
@@ -683,6 +687,93 @@ def deberta_rel_bias(c2p, p2c, c2p_idx, p2c_idx, B, L, inv_scale, out=None):
     return out
 
 
+_MONO = {}
+
+
+def check_rel_index_runs(c2p_idx, p2c_idx):
+    """host check behind deberta_rel_bias_bwd: along its second index every row of c2p_idx is
+    non-increasing and every row of p2c_idx non-decreasing, so all positions that map to one column
+    form ONE contiguous run (the kernel's single-writer sums depend on it). Raises ValueError."""
+    c = c2p_idx.detach().cpu().numpy() if isinstance(c2p_idx, torch.Tensor) else c2p_idx
+    p = p2c_idx.detach().cpu().numpy() if isinstance(p2c_idx, torch.Tensor) else p2c_idx
+    if c.ndim != 2 or p.ndim != 2 or c.shape != p.shape or c.shape[0] != c.shape[1]:
+        raise ValueError("deberta_rel_bias_bwd: c2p_idx / p2c_idx must be [L, L]")
+    if c.shape[1] > 1 and ((c[:, 1:] > c[:, :-1]).any() or (p[:, 1:] < p[:, :-1]).any()):
+        raise ValueError("deberta_rel_bias_bwd: the relative-position indices are not monotone along a row "
+                         "(c2p_idx non-increasing, p2c_idx non-decreasing): the run-sum kernel does not apply")
+    return int(max(c.max(), p.max())) if c.size else -1, int(min(c.min(), p.min())) if c.size else 0
+
+
+def verify_rel_indices(c2p_idx, p2c_idx, host=None):
+    """(max, min) index of a device index pair after check_rel_index_runs, once per pair (cached by
+    tensor identity and version). `host`: the pair's host copies (numpy), for a caller that built the
+    device tensors from them — no device read then, so the model registers its cached pair when it
+    creates it and a later graph capture finds it verified."""
+    key = (c2p_idx.data_ptr(), p2c_idx.data_ptr(), tuple(c2p_idx.shape), c2p_idx._version, p2c_idx._version)
+    ent = _MONO.get(key)
+    # (an entry counts only for the very tensors it was made for: a freed pair's addresses get reused)
+    if ent is not None and ent[1]() is c2p_idx and ent[2]() is p2c_idx:
+        return ent[0]
+    if host is None and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("deberta_rel_bias_bwd: the index pair must be verified before a graph capture "
+                           "(verify_rel_indices outside the capture)")
+    rng = check_rel_index_runs(*host) if host is not None else check_rel_index_runs(c2p_idx, p2c_idx)
+    if len(_MONO) > 64:
+        _MONO.clear()
+    _MONO[key] = (rng, weakref.ref(c2p_idx), weakref.ref(p2c_idx))
+    return rng
+
+
+def deberta_rel_bias_bwd(ds, c2p_idx, p2c_idx, B, L, inv_scale, ld, dtype, dc2p=None, dp2c=None):
+    """adjoint of deberta_rel_bias: ds fp32 [B, H, L, L] -> (dc2p, dp2c) [H, B*L, ld] in `dtype`.
+    The index pair is verified on the host once (cached by tensor identity: the model caches one
+    pair per (L, S)): monotone rows (check_rel_index_runs) and values in [0, ld)."""
+    _require_cuda(ds, c2p_idx, p2c_idx)
+    if ds.dtype != torch.float32 or not ds.is_contiguous() or ds.dim() != 4 or ds.shape[0] != B or ds.shape[2:] != (L, L):
+        raise ValueError("deberta_rel_bias_bwd: ds must be a contiguous fp32 [B, H, L, L] tensor")
+    for t in (c2p_idx, p2c_idx):
+        if t.dtype != torch.int32 or not t.is_contiguous() or tuple(t.shape) != (L, L):
+            raise ValueError("deberta_rel_bias_bwd: indices must be contiguous int32 [L, L]")
+    rng = verify_rel_indices(c2p_idx, p2c_idx)
+    if rng[0] >= ld or rng[1] < 0:
+        raise ValueError(f"deberta_rel_bias_bwd: indices span [{rng[1]}, {rng[0]}], outside [0, {ld})")
+    H = ds.shape[1]
+    dc2p = dc2p if dc2p is not None else torch.empty((H, B * L, ld), device=ds.device, dtype=dtype)
+    dp2c = dp2c if dp2c is not None else torch.empty((H, B * L, ld), device=ds.device, dtype=dtype)
+    for t in (dc2p, dp2c):
+        if t.dtype != dtype or tuple(t.shape) != (H, B * L, ld) or not t.is_contiguous():
+            raise ValueError("deberta_rel_bias_bwd: dc2p / dp2c must be contiguous [H, B*L, ld] of `dtype`")
+    _check(lib().mmfd_deberta_rel_bias_bwd(dtype_code(dtype), B, H, L, _ptr(ds), _ptr(c2p_idx), _ptr(p2c_idx),
+                                           float(inv_scale), _ptr(dc2p), _ptr(dp2c), ld, _stream()),
+           "mmfd_deberta_rel_bias_bwd")
+    return dc2p, dp2c
+
+
+def attn_fill_masked_rows_bwd(dout, H, mask, dv=None, gsum=None):
+    """adjoint of attn_fill_masked_rows in two calls around attn_bwd. Without `dv` (phase 0): returns
+    gsum [B, H*Dh] fp32 = (1/L) * the sum of dout over the padded query rows (mask[b, i] == 0), and
+    zeroes those rows of dout in place. With `dv` and that `gsum` (phase 1): dv[b, j] += gsum[b] for
+    every key j, in place; returns dv."""
+    _require_cuda(dout, mask, dv, gsum)
+    B, L, HD = dout.shape
+    Dh = HD // H
+    dop, dosb, dost = _head_view(dout, H, Dh)
+    if dv is None:
+        m = mask.to(torch.int64).contiguous()
+        gsum = torch.empty((B, HD), device=dout.device, dtype=torch.float32)
+        _check(lib().mmfd_attn_fill_masked_rows_bwd(dtype_code(dout.dtype), 0, B, H, L, Dh, dop, dosb, dost, None, 0, 0,
+                                                    _ptr(m), _ptr(gsum), _stream()), "mmfd_attn_fill_masked_rows_bwd")
+        return gsum
+    if gsum is None or gsum.dtype != torch.float32 or tuple(gsum.shape) != (B, HD) or not gsum.is_contiguous():
+        raise ValueError("attn_fill_masked_rows_bwd: phase 1 needs the gsum [B, H*Dh] of phase 0")
+    if dv.dtype != dout.dtype or tuple(dv.shape) != (B, L, HD):
+        raise ValueError("attn_fill_masked_rows_bwd: dv must match dout in shape and dtype")
+    dvp, dvsb, dvst = _head_view(dv, H, Dh)
+    _check(lib().mmfd_attn_fill_masked_rows_bwd(dtype_code(dv.dtype), 1, B, H, L, Dh, None, 0, 0, dvp, dvsb, dvst, None,
+                                                _ptr(gsum), _stream()), "mmfd_attn_fill_masked_rows_bwd")
+    return dv
+
+
 def mask_rows(x2d, mask):
     """x[r, :] = 0 where mask[r] == 0 (in place)"""
     _require_cuda(x2d, mask)
@@ -707,10 +798,12 @@ def attn_fill_masked_rows(v, o, H, mask):
 
 def attn_bwd(q, k, v, o, lse, dout, H, *, dq=None, dk=None, dv=None, scale=None, key_bias=None, rel_bias=None,
              dropout_p=0.0, seed=None, salt=0, accumulate_dq=False, accumulate_dkv=False, dqkv_planes=None,
-             planes_only=False, drop_mask=None):
+             planes_only=False, drop_mask=None, d_rel_bias=None):
     """dq, dk, dv (views of one packed [B, L, 3*H*D] buffer when `dqkv_planes` is given: bf16
     [3, B*L, 3*H*D] split planes of that buffer, written by the kernels; planes_only skips the
-    fp32 stores — for a gradient read only by split-operand GEMMs, see x6_ok)"""
+    fp32 stores — for a gradient read only by split-operand GEMMs, see x6_ok).
+    `d_rel_bias` (contiguous fp32 [B, H, Lq, Lk]): receives the gradient with respect to a per-batch
+    `rel_bias` [B, H, Lq, Lk] (no dropout; include/mmfd.h mmfd_attn_args.d_rel_bias)."""
     _require_cuda(q, k, v, o, lse, dout)
     B, Lq, HD = q.shape
     Lk = k.shape[1]
@@ -724,7 +817,7 @@ def attn_bwd(q, k, v, o, lse, dout, H, *, dq=None, dk=None, dv=None, scale=None,
     _ops().attn_bwd(q, k, v, o, lse, dout, dq, dk, dv, int(H), float(scale if scale is not None else D ** -0.5),
                     key_bias, rel_bias if rb is not None else None, int(rb_sb), int(rb_mod), float(dropout_p),
                     seed.t if seed is not None else None, _salt(salt), bool(accumulate_dq), bool(accumulate_dkv),
-                    dqkv_planes, bool(planes_only), drop_mask if dropout_p > 0 else None)
+                    dqkv_planes, bool(planes_only), drop_mask if dropout_p > 0 else None, d_rel_bias)
     return dq, dk, dv
 
 
@@ -908,6 +1001,23 @@ def embed_ln_infer(ids, pos_ids, word, pos, gamma, beta, eps, dtype, tts=None, t
                                       _ptr(typ) if typ is not None else None, _ptr(gamma), _ptr(beta), float(eps),
                                       None, _ptr(y), None, None, 0.0, None, 0, _stream()), "mmfd_embed_ln_fwd_ex")
     return y
+
+
+def embed_ln_train(ids, pos_ids, word, pos, gamma, beta, eps, dtype):
+    """embed_ln_infer that keeps what the LayerNorm backward reads: (sum, y, mean, rstd) with
+    sum = word[id] + pos[pos_id] before the LayerNorm (no type table, no dropout)"""
+    B, L = ids.shape
+    D = word.shape[1]
+    dev = ids.device
+    s = torch.empty((B * L, D), device=dev, dtype=dtype)
+    y = torch.empty((B * L, D), device=dev, dtype=dtype)
+    mean = torch.empty(B * L, device=dev, dtype=torch.float32)
+    rstd = torch.empty(B * L, device=dev, dtype=torch.float32)
+    _check(lib().mmfd_embed_ln_fwd_ex(dtype_code(dtype), B, L, D, _ptr(ids.contiguous()),
+                                      _ptr(pos_ids.contiguous()) if pos_ids is not None else None, None, _ptr(word),
+                                      _ptr(pos), None, _ptr(gamma), _ptr(beta), float(eps), _ptr(s), _ptr(y),
+                                      _ptr(mean), _ptr(rstd), 0.0, None, 0, _stream()), "mmfd_embed_ln_fwd_ex")
+    return s, y, mean, rstd
 
 
 def position_ids(ids, padding_idx):

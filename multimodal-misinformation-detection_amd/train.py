@@ -412,7 +412,7 @@ def parse_args(argv=None):
     ap.add_argument("--train_data", type=str, default="./data/preprocessed/train.csv")
     ap.add_argument("--val_data", type=str)
     ap.add_argument("--text_encoder", type=str, default="microsoft/deberta-v3-xsmall",
-                    help="microsoft/deberta-v3-xsmall (frozen) or bert-base-uncased")
+                    help="microsoft/deberta-v3-xsmall (frozen unless --train_text_encoder) or bert-base-uncased")
     ap.add_argument("--output_dir", type=str, default="./results")
     ap.add_argument("--save_every", type=int, default=2000)
     ap.add_argument("--log_every", type=int, default=100)
@@ -434,6 +434,9 @@ def parse_args(argv=None):
     # mmfd
     ap.add_argument("--image_encoder", type=str, default="microsoft/swinv2-base-patch4-window8-256",
                     help="microsoft/swinv2-base-patch4-window8-256 (frozen) or google/vit-base-patch16-224")
+    ap.add_argument("--train_text_encoder", action="store_true",
+                    help="fine-tune microsoft/deberta-v3-xsmall (no dropout) instead of freezing it; --freeze_text "
+                         "wins; no effect on bert-base-uncased, which trains unless --freeze_text")
     ap.add_argument("--precision", choices=["fp32", "bf16"], default="fp32")
     ap.add_argument("--synthetic", type=int, default=0,
                     help="train on N synthetic Factify-shaped pairs instead of --train_data")
@@ -448,12 +451,15 @@ IMAGE_ENCODERS = ("microsoft/swinv2-base-patch4-window8-256", "google/vit-base-p
 
 
 def build_encoders(args, device):
-    """the encoders of train.py:329-340 (random init: no hub download here). DeBERTa-v3 / Swinv2
-    are inference encoders in mmfd and therefore always frozen, as in the reference; bert-base /
-    ViT-B/16 train unless --freeze_text / --freeze_image."""
+    """the encoders of train.py:329-340 (random init: no hub download here). Swinv2 is an inference
+    encoder in mmfd and therefore always frozen, as in the reference; so is DeBERTa-v3 by default,
+    and with --train_text_encoder (and no --freeze_text) it is built trainable
+    (DebertaV2Config(trainable=True), dropout 0) and fine-tuned; bert-base / ViT-B/16 train unless
+    --freeze_text / --freeze_image."""
     if args.text_encoder == "microsoft/deberta-v3-xsmall":
         from .deberta import DebertaV2Config, DebertaV2Model
-        text, text_frozen = DebertaV2Model(DebertaV2Config()), True
+        trainable = bool(getattr(args, "train_text_encoder", False)) and not args.freeze_text
+        text, text_frozen = DebertaV2Model(DebertaV2Config(trainable=trainable)), not trainable
     elif args.text_encoder == "bert-base-uncased":
         text, text_frozen = BertModel(BertConfig()), args.freeze_text
     else:
