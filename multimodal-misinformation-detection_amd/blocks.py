@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import os
 import weakref
+from collections import namedtuple
 
 import torch
 
@@ -408,12 +409,13 @@ def new_planes(ctx: StepCtx, rows, cols, device):
     return torch.empty((3, rows, cols), device=device, dtype=torch.bfloat16)
 
 
-def out_planes(ctx: StepCtx, rows, cols, consumers, device):
+def out_planes(ctx: StepCtx, rows, cols, consumers, device, want=True):
     """(planes, write_out) for a GEMM output in split-operand fp32 mode: bf16 [3, rows, cols]
     written by the producing epilogue, and whether the fp32 output is needed at all — it is not
     when every consumer GEMM ((M, N, K, trans_a, trans_b) tuples) runs on split operands.
-    (None, True) otherwise."""
-    if ctx.dt != torch.float32 or K.fp32_gemm_mode() != 1 or cols % 8 or os.environ.get("MMFD_NO_EPI_PLANES"):
+    (None, True) otherwise, or when not `want`."""
+    if not want or ctx.dt != torch.float32 or K.fp32_gemm_mode() != 1 or cols % 8 \
+            or os.environ.get("MMFD_NO_EPI_PLANES"):
         return None, True
     pl = torch.empty((3, rows, cols), device=device, dtype=torch.bfloat16)
     return pl, not all(K.x6_ok(*c) for c in consumers)
@@ -484,12 +486,13 @@ def layernorm_planes(ctx: StepCtx, x2d, name, eps, want=True):
     return y, m, r, None
 
 
-def layernorm_bwd_planes(ctx: StepCtx, dy2d, x2d, name, mean, rstd, *, dx_add=None, drop_site=None):
+def layernorm_bwd_planes(ctx: StepCtx, dy2d, x2d, name, mean, rstd, *, dx_add=None, drop_site=None, want=True):
     """layernorm_bwd plus the split planes of the gradient the next GEMMs read (the dropped one when
-    there is dropout), written by the same kernel in split-operand fp32 mode (else None):
-    (dx, dx_dropped or None, planes or None)"""
+    there is dropout), written by the same kernel when `want` and in split-operand fp32 mode (else
+    None): (dx, dx_dropped or None, planes or None)"""
     W = dy2d.shape[1]
-    if not (ctx.dt == torch.float32 and W % 8 == 0 and W // 4 > 32 and K.split_eligible(dy2d)) or _NO_LN_PLANES:
+    if not (want and ctx.dt == torch.float32 and W % 8 == 0 and W // 4 > 32 and K.split_eligible(dy2d)) \
+            or _NO_LN_PLANES:
         dx, dd = layernorm_bwd(ctx, dy2d, x2d, name, mean, rstd, dx_add=dx_add, drop_site=drop_site)
         return dx, dd, None
     pl = torch.empty((3, dy2d.shape[0], W), device=dy2d.device, dtype=torch.bfloat16)
@@ -521,8 +524,7 @@ def mlp_ln_fwd(ctx: StepCtx, a2d, mlp, ln, site, eps=1e-5, w1=".net.0", w2=".net
     `want_planes` the LayerNorm also writes the output's planes. Returns (y, yp or None, state)."""
     T, E = a2d.shape
     I = ctx.P[mlp + w1 + ".weight"].shape[0]
-    hp, h_out = out_planes(ctx, T, I, [(T, E, I), (E, I, T, True, True)], a2d.device) if ap is not None \
-        else (None, True)
+    hp, h_out = out_planes(ctx, T, I, [(T, E, I), (E, I, T, True, True)], a2d.device, want=ap is not None)
     h, pre = linear(ctx, a2d, mlp + w1, act=K.ACT_GELU, keep_aux=True, drop_site=site + ".h", xp=ap, out_planes=hp,
                     write_out=h_out)
     s, _ = linear(ctx, h, mlp + w2, residual=a2d, drop_site=site + ".out", xp=hp)
@@ -532,19 +534,152 @@ def mlp_ln_fwd(ctx: StepCtx, a2d, mlp, ln, site, eps=1e-5, w1=".net.0", w2=".net
 
 def mlp_ln_bwd(ctx: StepCtx, dy2d, st):
     a2d, ap, h, hp, pre, s, mean, rstd, mlp, ln, site, w1, w2 = st
-    ds, ds_drop, gp = layernorm_bwd_planes(ctx, dy2d, s, ln, mean, rstd, drop_site=site + ".out") \
-        if ap is not None else (*layernorm_bwd(ctx, dy2d, s, ln, mean, rstd, drop_site=site + ".out"), None)
+    ds, ds_drop, gp = layernorm_bwd_planes(ctx, dy2d, s, ln, mean, rstd, drop_site=site + ".out", want=ap is not None)
     g_out = ds_drop if ds_drop is not None else ds
     ctx.lin_grads([mlp + w2], g_out, h, gp, hp)
     T, E = g_out.shape
     I = h.shape[1]
-    dprep, dpre_out = out_planes(ctx, T, I, [(I, E, T, True, True), (T, E, I, False, True)], g_out.device) \
-        if gp is not None else (None, True)
+    dprep, dpre_out = out_planes(ctx, T, I, [(I, E, T, True, True), (T, E, I, False, True)], g_out.device,
+                                 want=gp is not None)
     dpre = linear_dx(ctx, g_out, mlp + w2, act=K.ACT_GELU_BWD, aux=pre, drop_site=site + ".h", dyp=gp,
                      out_planes=dprep, write_out=dpre_out)
     ctx.lin_grads([mlp + w1], dpre, a2d, dprep, ap)
     linear_dx(ctx, dpre, mlp + w1, out=ds, beta=1.0, dyp=dprep)  # da = ds + dpre W1
     return ds
+
+
+# -------------------------------------------------------------------------------------------------
+# Transformer-layer pieces of the encoders (BERT, ViT, MPNet, DeBERTa-v3). Each forward returns a
+# record of what its backward reads (None unless `keep`). `planes`: the producers (LayerNorm, GEMM
+# epilogues, attention kernels) write the split-operand planes of what the next GEMMs read (fp32
+# split-operand mode; a no-op in bf16 / fp32-MFMA mode)
+# -------------------------------------------------------------------------------------------------
+# x (planes xp): FFN1 input; pre: what the GELU backward reads (see linear); f (planes fp): GELU output
+FFNState = namedtuple("FFNState", "x xp pre f fp w1 w2 planes")
+
+
+def ffn_fwd(ctx: StepCtx, x, w1, w2, *, residual, keep, planes, xp=None, drop_site=None):
+    """y = residual + drop(W2 gelu(W1 x + b1) + b2): (y, FFNState)"""
+    T, D = x.shape
+    I = ctx.P[w1 + ".weight"].shape[0]
+    # the GELU output feeds only the FFN2 forward and FFN2 weight-gradient GEMMs: its planes come
+    # from the FFN1 epilogue, and the fp32 copy is skipped when both run on split operands
+    fp, f_out = out_planes(ctx, T, I, [(T, D, I), (D, I, T, True, True)], x.device, want=planes)
+    f, pre = linear(ctx, x, w1, act=K.ACT_GELU, keep_aux=keep, xp=xp, out_planes=fp, write_out=f_out)
+    y, _ = linear(ctx, f, w2, residual=residual, drop_site=drop_site, xp=fp)
+    return y, FFNState(x, xp, pre, f, fp, w1, w2, planes) if keep else None
+
+
+def ffn_bwd(ctx: StepCtx, g, gp, st, residual=None):
+    """`g` (planes `gp`): gradient of the FFN2 product; returns residual + the FFN input's gradient"""
+    ctx.lin_grads([st.w2], g, st.f, gp, st.fp)
+    T, D = g.shape
+    I = st.pre.shape[1]
+    dprep, dpre_out = out_planes(ctx, T, I, [(I, D, T, True, True), (T, D, I, False, True)], g.device, want=st.planes)
+    dpre = linear_dx(ctx, g, st.w2, act=K.ACT_GELU_BWD, aux=st.pre, dyp=gp, out_planes=dprep, write_out=dpre_out)
+    ctx.lin_grads([st.w1], dpre, st.x, dprep, st.xp)
+    # residual + dpre W1 (a fresh buffer: the weight-gradient GEMM on the side stream may still be
+    # reading the residual)
+    return linear_dx(ctx, dpre, st.w1, residual=residual, dyp=dprep)
+
+
+def attn_out_bwd(ctx: StepCtx, name, g, gp, o, op):
+    """backward of the attention-output projection `name` of `o` (planes `op`): do, shaped like o"""
+    ctx.lin_grads([name], g, as2d(o), gp, op)
+    return linear_dx(ctx, g, name, dyp=gp).view(o.shape)
+
+
+def attn_bwd_packed(ctx: StepCtx, qkv, o, lse, do, H, *, planes, **kw):
+    """self-attention backward over the packed projections `qkv` [B, L, 3D] (`kw`: key_bias, rel_bias,
+    scale, d_rel_bias, dropout): the packed gradient [B*L, 3D], its planes or None, and whether only
+    the planes were written"""
+    D = o.shape[-1]
+    dqkv = torch.empty_like(qkv)
+    T = qkv.shape[0] * qkv.shape[1]
+    # the packed gradient feeds only the QKV dX / dW GEMMs: planes straight from the attention
+    # backward, and no fp32 copy when both run on split operands
+    dqp, dq_out = out_planes(ctx, T, 3 * D, [(3 * D, D, T, True, True), (T, D, 3 * D, False, True)], dqkv.device,
+                             want=planes)
+    K.attn_bwd(qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:], o, lse, do, H, dq=dqkv[..., :D],
+               dk=dqkv[..., D:2 * D], dv=dqkv[..., 2 * D:], dqkv_planes=dqp, planes_only=not dq_out, **kw)
+    return as2d(dqkv), dqp, not dq_out
+
+
+# x (planes xp): input of the packed projections `names`; qkv [B, L, 3D]; o [B, L, D]; kw: attn_fwd's keywords
+AttnState = namedtuple("AttnState", "x xp names qkv o lse H planes kw")
+
+
+def self_attn_fwd(ctx: StepCtx, x, names, B, H, *, keep, planes, xp=None, drop_site=None, **kw):
+    """packed Q|K|V projection of x [B*L, D] and self-attention (`kw`: key_bias, rel_bias):
+    (o [B, L, D], its planes or None, AttnState)"""
+    D = x.shape[1]
+    qkv = linear_packed(ctx, x, names, xp=xp).view(B, -1, 3 * D)
+    q, k, v = qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:]
+    if drop_site is not None:
+        kw.update(ctx.attn_drop(drop_site, q, k, H))
+    # the output's planes from the attention kernel itself (fp32 split-operand mode)
+    op = new_planes(ctx, x.shape[0], D, x.device) if planes else None
+    o, lse = K.attn_fwd(q, k, v, H, o_planes=op, **kw)
+    return o, op, AttnState(x, xp, names, qkv, o, lse, H, planes, kw) if keep else None
+
+
+def self_attn_bwd(ctx: StepCtx, do, st, residual=None):
+    """backward of self_attn_fwd: residual + dQKV [Wq;Wk;Wv], the gradient of x (a fresh buffer)"""
+    dqkv, dqp, planes_only = attn_bwd_packed(ctx, st.qkv, st.o, st.lse, do, st.H, planes=st.planes, **st.kw)
+    dqkv._mmfd_planes_only = planes_only
+    ctx.lin_grads(st.names, dqkv, st.x, dqp, st.xp)
+    Wp, _ = ctx.w_packed(st.names)
+    return linear_dx(ctx, dqkv, Wp, residual=residual, dyp=dqp)
+
+
+# o (planes op): attention output [B, L, D]; (s, m, r): a LayerNorm's input, mean, rstd; names: the output
+# projection and the two LayerNorms; sites: dropout sites of the two residual branches (None: no dropout)
+PostLNState = namedtuple("PostLNState", "o op s1 m1 r1 s2 m2 r2 ffn names sites")
+
+
+def post_ln_fwd(ctx: StepCtx, x, o, p, suffixes, eps, *, keep, planes, y_planes=False, op=None, sites=(None, None)):
+    """The post-LN layer after its self-attention: h = LN(x + drop(Wo o)), y = LN(h + drop(FFN(h))).
+    `suffixes` of `p` name the output projection, its LayerNorm, FFN1, FFN2 and the output
+    LayerNorm. Returns (y, its planes when `planes and y_planes` else None, PostLNState)"""
+    out, ln1, w1, w2, ln2 = (p + s for s in suffixes)
+    s1, _ = linear(ctx, as2d(o), out, residual=x, drop_site=sites[0], xp=op)
+    h, m1, r1, hp = layernorm_planes(ctx, s1, ln1, eps, want=planes)
+    s2, ffn = ffn_fwd(ctx, h, w1, w2, residual=h, keep=keep, planes=planes, xp=hp, drop_site=sites[1])
+    y, m2, r2, yp = layernorm_planes(ctx, s2, ln2, eps, want=planes and y_planes)
+    return y, yp, PostLNState(o, op, s1, m1, r1, s2, m2, r2, ffn, (out, ln1, ln2), sites) if keep else None
+
+
+def post_ln_bwd(ctx: StepCtx, dy, st: PostLNState):
+    """(do, ds1): the gradients of the attention output and of the first residual sum (the layer
+    input's share; the caller adds its attention backward's)"""
+    out, ln1, ln2 = st.names
+    planes = st.ffn.planes
+    ds2, ds2d, g2p = layernorm_bwd_planes(ctx, dy, st.s2, ln2, st.m2, st.r2, drop_site=st.sites[1], want=planes)
+    dh = ffn_bwd(ctx, ds2d if ds2d is not None else ds2, g2p, st.ffn, residual=ds2)
+    ds1, ds1d, g1p = layernorm_bwd_planes(ctx, dh, st.s1, ln1, st.m1, st.r1, drop_site=st.sites[0], want=planes)
+    return attn_out_bwd(ctx, out, ds1d if ds1d is not None else ds1, g1p, st.o, st.op), ds1
+
+
+# -------------------------------------------------------------------------------------------------
+# one-node autograd Functions of the trainable encoders
+# -------------------------------------------------------------------------------------------------
+def module_ctx(model, names, params, dropout_p=0.0, seed=None):
+    """the StepCtx of one forward/backward of `model` over its parameters (detached)"""
+    P = {n: p.detach() for n, p in zip(names, params)}
+    sc = StepCtx(P, model.compute_dtype, dropout_p, seed, training=model.training, shadows=shadow_store(model))
+    sc.grad_ready = getattr(model, "_grad_ready", None)
+    return sc
+
+
+def fn_backward(fctx, dout, backward):
+    """`backward(sc, dout)` fills fctx.sc.grads: the gradients of fctx.names, and the saved state is dropped"""
+    sc = fctx.sc
+    sc.enable_side_stream(dout.device)
+    backward(sc, dout.to(sc.dt))
+    sc.join_side()
+    grads = [sc.grads.get(n) for n in fctx.names]
+    fctx.sc = fctx.st = None
+    return grads
 
 
 def load_state_dict_checked(module, state_dict, benign=("position_ids", "num_batches_tracked")):

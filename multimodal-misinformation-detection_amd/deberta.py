@@ -22,7 +22,8 @@ flash-attention kernels consume (batch-strided rel_bias); padded-row fix-ups are
 By default inference only (the reference freezes its encoders, train.py:335-340, and the
 pre-embedding pass runs under no_grad): a forward that would need gradients raises. With
 `DebertaV2Config(trainable=True)` a forward under grad runs as ONE autograd node (`_DebertaFn`, shaped
-like encoders._BertFn) whose backward is `deberta_backward`: the post-LN block backward of BERT, and
+like encoders._BertFn) whose backward is `deberta_backward`: the post-LN layer backward BERT also runs
+(blocks.post_ln_bwd) and the shared attention backward into a packed gradient (blocks.attn_bwd_packed), and
 through the disentangled bias the attention backward's dS (mmfd_attn_args.d_rel_bias), its scatter
 back to dc2p / dp2c (mmfd_deberta_rel_bias_bwd), four per-head GEMMs into dQ, dK and the position
 projections' gradients, and the padded-row fix-up's adjoint (mmfd_attn_fill_masked_rows_bwd). Each
@@ -32,6 +33,7 @@ this path (HF's default is 0.1): the config's dropout probabilities must be 0 wh
 from __future__ import annotations
 
 import math
+from collections import namedtuple
 from dataclasses import dataclass
 
 import numpy as np
@@ -40,7 +42,7 @@ import torch.nn as nn
 
 from . import blocks as Bk
 from . import kernels as K
-from .encoders import EncoderOutput
+from .encoders import BERT_LAYER, EncoderOutput
 
 
 @dataclass
@@ -181,6 +183,13 @@ class DebertaV2Model(Bk.CachedWeights, nn.Module):
         return EncoderOutput(last_hidden_state=out)
 
 
+DEBERTA_QKV = (".attention.self.query_proj", ".attention.self.key_proj", ".attention.self.value_proj")
+
+
+# x: layer input; qkv [B, L, 3D]; pos [2S, 3D]: position projections; rb [B, H, L, L] fp32: disentangled bias
+DebertaLayerState = namedtuple("DebertaLayerState", "x qkv pos rb lse post")
+
+
 def deberta_forward(model: DebertaV2Model, ctx: Bk.StepCtx, input_ids, attention_mask, st=None):
     """`st` (a dict, training): filled with what deberta_backward reads; the kernels and their order
     are the same either way, so the outputs are too"""
@@ -217,7 +226,7 @@ def deberta_forward(model: DebertaV2Model, ctx: Bk.StepCtx, input_ids, attention
     p2c = torch.empty((H, B * L, 2 * S), device=dev, dtype=dt)
     for i in range(cfg.num_hidden_layers):
         p = f"encoder.layer.{i}"
-        names = [p + ".attention.self.query_proj", p + ".attention.self.key_proj", p + ".attention.self.value_proj"]
+        names = [p + n for n in DEBERTA_QKV]
         qkv = Bk.linear_packed(ctx, x, names)                # [B*L, 3D]
         pos = Bk.linear_packed(ctx, relE, names)             # [2S, 3D]: posQ | posK | (unused V)
         for h in range(H):
@@ -230,13 +239,9 @@ def deberta_forward(model: DebertaV2Model, ctx: Bk.StepCtx, input_ids, attention
         o, lse = K.attn_fwd(q3[..., :D], q3[..., D:2 * D], q3[..., 2 * D:], H, scale=scale, key_bias=key_bias,
                             rel_bias=rb)
         K.attn_fill_masked_rows(q3[..., 2 * D:], o, H, mask)
-        s1, _ = Bk.linear(ctx, Bk.as2d(o), p + ".attention.output.dense", residual=x)
-        h1, m1, r1 = Bk.layernorm(ctx, s1, p + ".attention.output.LayerNorm", eps)
-        f, pre = Bk.linear(ctx, h1, p + ".intermediate.dense", act=K.ACT_GELU, keep_aux=keep)
-        s2, _ = Bk.linear(ctx, f, p + ".output.dense", residual=h1)
-        x_out, m2, r2 = Bk.layernorm(ctx, s2, p + ".output.LayerNorm", eps)
+        x_out, _, post = Bk.post_ln_fwd(ctx, x, o, p, BERT_LAYER, eps, keep=keep, planes=False)
         if keep:
-            st["layers"].append((x, qkv, pos, rb, o, lse, s1, m1, r1, h1, pre, f, s2, m2, r2))
+            st["layers"].append(DebertaLayerState(x, q3, pos, rb, lse, post))
         x = x_out
     if keep:
         st.update(ids=ids, mask=mask, key_bias=key_bias, idx=(c2p_idx, p2c_idx), s0=s0, m0=m0, r0=r0, rel_in=rel_in,
@@ -245,8 +250,8 @@ def deberta_forward(model: DebertaV2Model, ctx: Bk.StepCtx, input_ids, attention
 
 
 def deberta_backward(model: DebertaV2Model, ctx: Bk.StepCtx, dout, st):
-    """Gradients of every parameter into ctx.grads, layers in reverse. Per layer: the BERT block
-    backward (FFN, both LayerNorms, output projection), then through the attention
+    """Gradients of every parameter into ctx.grads, layers in reverse. Per layer: blocks.post_ln_bwd
+    (FFN, both LayerNorms, output projection), then through the attention
         S = scale Q K^T + key_bias + inv (c2p[i, c2p_idx[i, j]] + p2c[j, p2c_idx[j, i]])
     with c2p = Q_h posK_h^T, p2c = K_h posQ_h^T: attn_bwd also emits dS (no dropout), its scatter
     gives dc2p / dp2c, and per head dQ_h += dc2p_h posK_h, dK_h += dp2c_h posQ_h, dposK_h =
@@ -268,24 +273,15 @@ def deberta_backward(model: DebertaV2Model, ctx: Bk.StepCtx, dout, st):
     dc2p, dp2c = st["bufs"]                     # the forward's c2p / p2c buffers, free by now
     drelE = torch.empty((S2, D), device=dev, dtype=torch.float32)
     for i in reversed(range(cfg.num_hidden_layers)):
-        p = f"encoder.layer.{i}"
-        x, qkv, pos, rb, o, lse, s1, m1, r1, h1, pre, f, s2, m2, r2 = st["layers"][i]
+        ls = st["layers"][i]
         st["layers"][i] = None
-        ds2, _ = Bk.layernorm_bwd(ctx, dx, s2, p + ".output.LayerNorm", m2, r2)
-        ctx.lin_grads([p + ".output.dense"], ds2, f)
-        dpre = Bk.linear_dx(ctx, ds2, p + ".output.dense", act=K.ACT_GELU_BWD, aux=pre)
-        ctx.lin_grads([p + ".intermediate.dense"], dpre, h1)
-        dh1 = Bk.linear_dx(ctx, dpre, p + ".intermediate.dense", residual=ds2)
-        ds1, _ = Bk.layernorm_bwd(ctx, dh1, s1, p + ".attention.output.LayerNorm", m1, r1)
-        ctx.lin_grads([p + ".attention.output.dense"], ds1, Bk.as2d(o))
-        do = Bk.linear_dx(ctx, ds1, p + ".attention.output.dense").view(B, L, D)
+        qkv, pos = Bk.as2d(ls.qkv), ls.pos
+        do, ds1 = Bk.post_ln_bwd(ctx, dx, ls.post)
         # padded query rows: their dO goes to dV of every key (mean of V in the forward), not into the attention
         gsum = K.attn_fill_masked_rows_bwd(do, H, mask)
-        dqkv = torch.empty_like(qkv)
-        q3, dq3 = qkv.view(B, L, 3 * D), dqkv.view(B, L, 3 * D)
-        K.attn_bwd(q3[..., :D], q3[..., D:2 * D], q3[..., 2 * D:], o, lse, do, H, scale=scale, key_bias=st["key_bias"],
-                   rel_bias=rb, dq=dq3[..., :D], dk=dq3[..., D:2 * D], dv=dq3[..., 2 * D:], d_rel_bias=dsb)
-        K.attn_fill_masked_rows_bwd(do, H, mask, dv=dq3[..., 2 * D:], gsum=gsum)
+        dqkv, _, _ = Bk.attn_bwd_packed(ctx, ls.qkv, ls.post.o, ls.lse, do, H, planes=False, scale=scale,
+                                        key_bias=st["key_bias"], rel_bias=ls.rb, d_rel_bias=dsb)
+        K.attn_fill_masked_rows_bwd(do, H, mask, dv=dqkv.view(B, L, 3 * D)[..., 2 * D:], gsum=gsum)
         K.deberta_rel_bias_bwd(dsb, c2p_idx, p2c_idx, B, L, scale, S2, dt, dc2p=dc2p, dp2c=dp2c)
         dpos = torch.empty((S2, 2 * D), device=dev, dtype=dt)  # dposQ | dposK (the V third of pos is unused)
         for h in range(H):
@@ -294,8 +290,9 @@ def deberta_backward(model: DebertaV2Model, ctx: Bk.StepCtx, dout, st):
             K.gemm(dp2c[h], pos[:, hq], trans_b=True, out=dqkv[:, hk], beta=1.0)   # dK_h += dp2c_h posQ_h
             K.gemm(dc2p[h], qkv[:, hq], trans_a=True, trans_b=True, out=dpos[:, hk])  # dposK_h = dc2p_h^T Q_h
             K.gemm(dp2c[h], qkv[:, hk], trans_a=True, trans_b=True, out=dpos[:, hq])  # dposQ_h = dp2c_h^T K_h
-        names = [p + ".attention.self.query_proj", p + ".attention.self.key_proj", p + ".attention.self.value_proj"]
-        ctx.lin_grads(names, dqkv, x)                   # token stream (one packed GEMM)
+        names = [f"encoder.layer.{i}" + n for n in DEBERTA_QKV]
+        # (as blocks.self_attn_bwd, with the position stream's GEMMs between the weight and data gradients)
+        ctx.lin_grads(names, dqkv, ls.x)                # token stream (one packed GEMM)
         ctx.lin_grads(names[:2], dpos, relE)            # position stream: accumulates onto the Q and K blocks
         Wp, _ = ctx.w_packed(names)
         K.gemm(dpos, Wp[:2 * D], trans_b=True, out=drelE, beta=0.0 if i == cfg.num_hidden_layers - 1 else 1.0)
@@ -319,9 +316,7 @@ def deberta_backward(model: DebertaV2Model, ctx: Bk.StepCtx, dout, st):
 class _DebertaFn(torch.autograd.Function):
     @staticmethod
     def forward(fctx, model, names, input_ids, attention_mask, *params):
-        P = {n: p.detach() for n, p in zip(names, params)}
-        sc = Bk.StepCtx(P, model.compute_dtype, 0.0, None, training=model.training, shadows=Bk.shadow_store(model))
-        sc.grad_ready = getattr(model, "_grad_ready", None)
+        sc = Bk.module_ctx(model, names, params)
         st = {"layers": []}
         out = deberta_forward(model, sc, input_ids, attention_mask, st=st)
         fctx.sc, fctx.st, fctx.model, fctx.names = sc, st, model, names
@@ -329,10 +324,5 @@ class _DebertaFn(torch.autograd.Function):
 
     @staticmethod
     def backward(fctx, dout):
-        sc = fctx.sc
-        sc.enable_side_stream(dout.device)
-        deberta_backward(fctx.model, sc, dout.to(sc.dt), fctx.st)
-        sc.join_side()
-        grads = [sc.grads.get(n) for n in fctx.names]
-        fctx.sc = fctx.st = None
+        grads = Bk.fn_backward(fctx, dout, lambda sc, d: deberta_backward(fctx.model, sc, d, fctx.st))
         return (None, None, None, None, *grads)

@@ -10,6 +10,7 @@ bias, residual adds and dropout in GEMM epilogues, LayerNorm backward with fused
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from dataclasses import dataclass, field
 
 import torch
@@ -131,6 +132,12 @@ class BertModel(Bk.CachedWeights, nn.Module):
         return EncoderOutput(last_hidden_state=out)
 
 
+BERT_QKV = (".attention.self.query", ".attention.self.key", ".attention.self.value")
+# blocks.post_ln_fwd's parameter names of a layer: output projection, its LayerNorm, FFN1, FFN2, output LayerNorm
+BERT_LAYER = (".attention.output.dense", ".attention.output.LayerNorm", ".intermediate.dense", ".output.dense",
+              ".output.LayerNorm")
+
+
 def bert_forward(ctx: Bk.StepCtx, cfg: BertConfig, ids, mask, tts, keep, site="bert"):
     B, L = ids.shape
     D, H = cfg.hidden_size, cfg.num_attention_heads
@@ -150,72 +157,23 @@ def bert_forward(ctx: Bk.StepCtx, cfg: BertConfig, ids, mask, tts, keep, site="b
         # split-operand fp32 GEMMs: every Linear input is split once (by its producer: LayerNorm,
         # GEMM epilogue, else split3) and the planes are kept for its weight-gradient GEMM (None in
         # bf16 / fp32-MFMA mode)
-        qkv = Bk.linear_packed(ctx, x, [p + ".attention.self.query", p + ".attention.self.key",
-                                        p + ".attention.self.value"], xp=xp).view(B, L, 3 * D)
-        q, k, v = qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:]
-        attn_drop = dict(ctx.attn_drop(s + ".attn", q, k, H)) if cfg.attention_probs_dropout_prob > 0 else {}
-        # the output's planes from the attention kernel itself (fp32 split-operand mode)
-        op = Bk.new_planes(ctx, B * L, D, q.device) if keep else None
-        o, lse = K.attn_fwd(q, k, v, H, key_bias=kb, o_planes=op, **attn_drop)
-        s1, _ = Bk.linear(ctx, Bk.as2d(o), p + ".attention.output.dense", residual=x, drop_site=s + ".attn_out",
-                          xp=op)
-        h1, m1, r1, h1p = Bk.layernorm_planes(ctx, s1, p + ".attention.output.LayerNorm", eps, want=keep)
-        T_, I_ = h1.shape[0], cfg.intermediate_size
-        # the GELU output feeds only the FFN2 forward and FFN2 weight-gradient GEMMs: its planes come
-        # from the FFN1 epilogue, and the fp32 copy is skipped when both run on split operands
-        fp, f_out = Bk.out_planes(ctx, T_, I_, [(T_, D, I_), (D, I_, T_, True, True)], h1.device) if keep \
-            else (None, True)
-        f, pre = Bk.linear(ctx, h1, p + ".intermediate.dense", act=K.ACT_GELU, keep_aux=keep, xp=h1p,
-                           out_planes=fp, write_out=f_out)
-        s2, _ = Bk.linear(ctx, f, p + ".output.dense", residual=h1, drop_site=s + ".ffn_out", xp=fp)
-        x_out, m2, r2, xp_next = Bk.layernorm_planes(ctx, s2, p + ".output.LayerNorm", eps,
-                                                     want=keep and i + 1 < cfg.num_hidden_layers)
-        if keep:
-            states.append((x, qkv, o, lse, s1, m1, r1, h1, pre, f, s2, m2, r2, attn_drop, (xp, op, h1p, fp)))
-        x, xp = x_out, xp_next
-    st = dict(s0=s0, m0=m0, r0=r0, kb=kb, layers=states, emb_drop=emb_drop) if keep else None
+        o, op, attn = Bk.self_attn_fwd(ctx, x, [p + n for n in BERT_QKV], B, H, keep=keep, planes=keep, xp=xp,
+                                       drop_site=s + ".attn" if cfg.attention_probs_dropout_prob > 0 else None,
+                                       key_bias=kb)
+        x, xp, post = Bk.post_ln_fwd(ctx, x, o, p, BERT_LAYER, eps, keep=keep, planes=keep,
+                                     y_planes=i + 1 < cfg.num_hidden_layers, op=op,
+                                     sites=(s + ".attn_out", s + ".ffn_out"))
+        states.append((attn, post))
+    st = dict(s0=s0, m0=m0, r0=r0, layers=states, emb_drop=emb_drop) if keep else None
     return x.view(B, L, D), st
 
 
 def bert_backward(ctx: Bk.StepCtx, cfg: BertConfig, dout, st, ids, tts, site="bert"):
-    B, L = ids.shape
-    D, H = cfg.hidden_size, cfg.num_attention_heads
     dx = Bk.as2d(dout).contiguous()
     for i in reversed(range(cfg.num_hidden_layers)):
-        p = f"encoder.layer.{i}"
-        s = f"{site}.L{i}"
-        x, qkv, o, lse, s1, m1, r1, h1, pre, f, s2, m2, r2, attn_drop, (xp, op, h1p, fp) = st["layers"][i]
-        ds2, ds2d, g2p = Bk.layernorm_bwd_planes(ctx, dx, s2, p + ".output.LayerNorm", m2, r2, drop_site=s + ".ffn_out")
-        g2 = ds2d if ds2d is not None else ds2
-        ctx.lin_grads([p + ".output.dense"], g2, f, g2p, fp)
-        T_, I_ = g2.shape[0], cfg.intermediate_size
-        dprep, dpre_out = Bk.out_planes(ctx, T_, I_, [(I_, D, T_, True, True), (T_, D, I_, False, True)], g2.device)
-        dpre = Bk.linear_dx(ctx, g2, p + ".output.dense", act=K.ACT_GELU_BWD, aux=pre, dyp=g2p, out_planes=dprep,
-                            write_out=dpre_out)
-        ctx.lin_grads([p + ".intermediate.dense"], dpre, h1, dprep, h1p)
-        # dh1 = ds2 + dpre W (a fresh buffer: the weight-gradient GEMM on the side stream may still be
-        # reading ds2)
-        dh1 = Bk.linear_dx(ctx, dpre, p + ".intermediate.dense", residual=ds2, dyp=dprep)
-        ds1, ds1d, g1p = Bk.layernorm_bwd_planes(ctx, dh1, s1, p + ".attention.output.LayerNorm", m1, r1,
-                                                 drop_site=s + ".attn_out")
-        g1 = ds1d if ds1d is not None else ds1
-        ctx.lin_grads([p + ".attention.output.dense"], g1, Bk.as2d(o), g1p, op)
-        do = Bk.linear_dx(ctx, g1, p + ".attention.output.dense", dyp=g1p).view(o.shape)
-        dqkv = torch.empty_like(qkv)
-        # the packed gradient feeds only the QKV dX / dW GEMMs: planes straight from the attention
-        # backward, and no fp32 copy when both run on split operands
-        T_ = B * L
-        dq2p, dq_out = Bk.out_planes(ctx, T_, 3 * D, [(3 * D, D, T_, True, True), (T_, D, 3 * D, False, True)],
-                                     dqkv.device)
-        K.attn_bwd(qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:], o, lse, do, H, key_bias=st["kb"],
-                   dq=dqkv[..., :D], dk=dqkv[..., D:2 * D], dv=dqkv[..., 2 * D:], dqkv_planes=dq2p,
-                   planes_only=not dq_out, **attn_drop)
-        names = [p + ".attention.self.query", p + ".attention.self.key", p + ".attention.self.value"]
-        dq2 = Bk.as2d(dqkv)
-        dq2._mmfd_planes_only = not dq_out
-        ctx.lin_grads(names, dq2, x, dq2p, xp)
-        Wp, _ = ctx.w_packed(names)
-        dx = Bk.linear_dx(ctx, dq2, Wp, residual=ds1, dyp=dq2p)  # dx_in = ds1 + dQKV [Wq;Wk;Wv] (fresh buffer)
+        attn, post = st["layers"][i]
+        do, ds1 = Bk.post_ln_bwd(ctx, dx, post)
+        dx = Bk.self_attn_bwd(ctx, do, attn, residual=ds1)  # dx_in = ds1 + dQKV [Wq;Wk;Wv]
         ctx.flush_ready()
     # embeddings: undo the embedding dropout, LayerNorm backward, scatter into the tables
     if st["emb_drop"]:
@@ -236,17 +194,13 @@ class _BertFn(torch.autograd.Function):
     @staticmethod
     def forward(fctx, model, names, keep, input_ids, attention_mask, token_type_ids, *params):
         cfg = model.config
-        P = {n: p.detach() for n, p in zip(names, params)}
         training = model.training
         p = cfg.hidden_dropout_prob if training else 0.0
         if training and cfg.attention_probs_dropout_prob != cfg.hidden_dropout_prob:
             raise NotImplementedError("mmfd BERT uses one dropout probability for hidden and attention dropout")
         dev = params[0].device
-        sc = Bk.StepCtx(P, model.compute_dtype, p, model._fork_seed(dev) if training and p > 0 else None,
-                        training=training, shadows=Bk.shadow_store(model))
-        sc.grad_ready = getattr(model, "_grad_ready", None)
+        sc = Bk.module_ctx(model, names, params, p, model._fork_seed(dev) if training and p > 0 else None)
         ids = input_ids.to(dev).long().contiguous()
-        B, L = ids.shape
         mask = attention_mask.to(dev).long().contiguous() if attention_mask is not None else None
         tts = token_type_ids.to(dev).long().contiguous() if token_type_ids is not None else None  # None = type 0
         out, st = bert_forward(sc, cfg, ids, mask, tts, keep)
@@ -257,12 +211,8 @@ class _BertFn(torch.autograd.Function):
 
     @staticmethod
     def backward(fctx, dout):
-        sc = fctx.sc
-        sc.enable_side_stream(dout.device)
-        bert_backward(sc, fctx.model.config, dout.to(sc.dt), fctx.st, fctx.ids, fctx.tts)
-        sc.join_side()
-        grads = [sc.grads.get(n) for n in fctx.names]
-        fctx.sc = fctx.st = None
+        grads = Bk.fn_backward(fctx, dout, lambda sc, d: bert_backward(sc, fctx.model.config, d, fctx.st, fctx.ids,
+                                                                       fctx.tts))
         return (None, None, None, None, None, None, *grads)
 
 
@@ -333,6 +283,11 @@ class ViTModel(Bk.CachedWeights, nn.Module):
 
 
 PATCH_W = "embeddings.patch_embeddings.projection.weight"
+VIT_QKV = (".attention.attention.query", ".attention.attention.key", ".attention.attention.value")
+
+
+# x, x1: layer input and first residual sum, the inputs of layernorm_before (mean mb, rstd rb) / _after (ma, ra)
+ViTLayerState = namedtuple("ViTLayerState", "x mb rb attn op x1 ma ra ffn")
 
 
 def vit_forward(ctx: Bk.StepCtx, cfg: ViTConfig, px, keep):
@@ -349,20 +304,13 @@ def vit_forward(ctx: Bk.StepCtx, cfg: ViTConfig, px, keep):
     for i in range(cfg.num_hidden_layers):
         p = f"encoder.layer.{i}"
         h, mb, rb, hp = Bk.layernorm_planes(ctx, x, p + ".layernorm_before", eps, want=keep)  # (see BERT)
-        qkv = Bk.linear_packed(ctx, h, [p + ".attention.attention.query", p + ".attention.attention.key",
-                                        p + ".attention.attention.value"], xp=hp).view(B, T, 3 * D)
-        op = Bk.new_planes(ctx, B * T, D, qkv.device) if keep else None
-        o, lse = K.attn_fwd(qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:], H, o_planes=op)
+        o, op, attn = Bk.self_attn_fwd(ctx, h, [p + n for n in VIT_QKV], B, H, keep=keep, planes=keep, xp=hp)
         x1, _ = Bk.linear(ctx, Bk.as2d(o), p + ".attention.output.dense", residual=x, xp=op)
         h2, ma, ra, h2p = Bk.layernorm_planes(ctx, x1, p + ".layernorm_after", eps, want=keep)
-        T_, I_ = h2.shape[0], cfg.intermediate_size
-        fp, f_out = Bk.out_planes(ctx, T_, I_, [(T_, D, I_), (D, I_, T_, True, True)], h2.device) if keep \
-            else (None, True)  # GELU output planes from the FFN1 epilogue (see BERT)
-        f, pre = Bk.linear(ctx, h2, p + ".intermediate.dense", act=K.ACT_GELU, keep_aux=keep, xp=h2p,
-                           out_planes=fp, write_out=f_out)
-        x2, _ = Bk.linear(ctx, f, p + ".output.dense", residual=x1, xp=fp)
+        x2, ffn = Bk.ffn_fwd(ctx, h2, p + ".intermediate.dense", p + ".output.dense", residual=x1, keep=keep,
+                             planes=keep, xp=h2p)
         if keep:
-            states.append((x, h, mb, rb, qkv, o, lse, x1, h2, ma, ra, pre, f, (hp, op, h2p, fp)))
+            states.append(ViTLayerState(x, mb, rb, attn, op, x1, ma, ra, ffn))
         x = x2
     y, mf, rf = Bk.layernorm(ctx, x, "layernorm", eps)
     st = dict(patches=patches, layers=states, x_last=x, mf=mf, rf=rf, B=B, T=T) if keep else None
@@ -370,39 +318,21 @@ def vit_forward(ctx: Bk.StepCtx, cfg: ViTConfig, px, keep):
 
 
 def vit_backward(ctx: Bk.StepCtx, cfg: ViTConfig, dout, st):
-    D, H = cfg.hidden_size, cfg.num_attention_heads
+    D = cfg.hidden_size
     dx, _, dxp = Bk.layernorm_bwd_planes(ctx, Bk.as2d(dout).contiguous(), st["x_last"], "layernorm", st["mf"],
                                          st["rf"])
     for i in reversed(range(cfg.num_hidden_layers)):
         p = f"encoder.layer.{i}"
-        x, h, mb, rb, qkv, o, lse, x1, h2, ma, ra, pre, f, (hp, op, h2p, fp) = st["layers"][i]
+        ls = st["layers"][i]
         if dxp is None:
             dxp = ctx.planes(dx)
-        ctx.lin_grads([p + ".output.dense"], dx, f, dxp, fp)
-        T_, I_ = dx.shape[0], cfg.intermediate_size
-        dprep, dpre_out = Bk.out_planes(ctx, T_, I_, [(I_, D, T_, True, True), (T_, D, I_, False, True)], dx.device)
-        dpre = Bk.linear_dx(ctx, dx, p + ".output.dense", act=K.ACT_GELU_BWD, aux=pre, dyp=dxp, out_planes=dprep,
-                            write_out=dpre_out)
-        ctx.lin_grads([p + ".intermediate.dense"], dpre, h2, dprep, h2p)
-        dh2 = Bk.linear_dx(ctx, dpre, p + ".intermediate.dense", dyp=dprep)
-        dx1, _, dx1p = Bk.layernorm_bwd_planes(ctx, dh2, x1, p + ".layernorm_after", ma, ra, dx_add=dx)
+        dh2 = Bk.ffn_bwd(ctx, dx, dxp, ls.ffn)
+        dx1, _, dx1p = Bk.layernorm_bwd_planes(ctx, dh2, ls.x1, p + ".layernorm_after", ls.ma, ls.ra, dx_add=dx)
         if dx1p is None:
             dx1p = ctx.planes(dx1)
-        ctx.lin_grads([p + ".attention.output.dense"], dx1, Bk.as2d(o), dx1p, op)
-        do = Bk.linear_dx(ctx, dx1, p + ".attention.output.dense", dyp=dx1p).view(o.shape)
-        dqkv = torch.empty_like(qkv)
-        T_ = qkv.shape[0] * qkv.shape[1]  # planes of the packed gradient from the kernels (see BERT)
-        dq2p, dq_out = Bk.out_planes(ctx, T_, 3 * D, [(3 * D, D, T_, True, True), (T_, D, 3 * D, False, True)],
-                                     dqkv.device)
-        K.attn_bwd(qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:], o, lse, do, H, dq=dqkv[..., :D],
-                   dk=dqkv[..., D:2 * D], dv=dqkv[..., 2 * D:], dqkv_planes=dq2p, planes_only=not dq_out)
-        names = [p + ".attention.attention.query", p + ".attention.attention.key", p + ".attention.attention.value"]
-        dq2 = Bk.as2d(dqkv)
-        dq2._mmfd_planes_only = not dq_out
-        ctx.lin_grads(names, dq2, h, dq2p, hp)
-        Wp, _ = ctx.w_packed(names)
-        dh = Bk.linear_dx(ctx, dq2, Wp, dyp=dq2p)
-        dx, _, dxp = Bk.layernorm_bwd_planes(ctx, dh, x, p + ".layernorm_before", mb, rb, dx_add=dx1)
+        do = Bk.attn_out_bwd(ctx, p + ".attention.output.dense", dx1, dx1p, ls.attn.o, ls.op)
+        dh = Bk.self_attn_bwd(ctx, do, ls.attn)
+        dx, _, dxp = Bk.layernorm_bwd_planes(ctx, dh, ls.x, p + ".layernorm_before", ls.mb, ls.rb, dx_add=dx1)
         ctx.flush_ready()
     dpatch, dcls, dpos = K.vit_tokens_bwd(dx.view(st["B"], st["T"], D))
     ctx.grads["embeddings.cls_token"] = dcls.view(1, 1, D)
@@ -414,11 +344,9 @@ def vit_backward(ctx: Bk.StepCtx, cfg: ViTConfig, dout, st):
 class _ViTFn(torch.autograd.Function):
     @staticmethod
     def forward(fctx, model, names, keep, pixel_values, *params):
-        P = {n: p.detach() for n, p in zip(names, params)}
-        P[PATCH_W] = P[PATCH_W].reshape(P[PATCH_W].shape[0], -1)  # conv16/s16 == GEMM over patches
+        sc = Bk.module_ctx(model, names, params)
+        sc.P[PATCH_W] = sc.P[PATCH_W].reshape(sc.P[PATCH_W].shape[0], -1)  # conv16/s16 == GEMM over patches
         dev = params[0].device
-        sc = Bk.StepCtx(P, model.compute_dtype, 0.0, None, training=model.training, shadows=Bk.shadow_store(model))
-        sc.grad_ready = getattr(model, "_grad_ready", None)
         out, st = vit_forward(sc, model.config, pixel_values.to(dev).float().contiguous(), keep)
         fctx.keep = keep
         if keep:
@@ -428,13 +356,9 @@ class _ViTFn(torch.autograd.Function):
 
     @staticmethod
     def backward(fctx, dout):
-        sc = fctx.sc
-        sc.enable_side_stream(dout.device)
-        vit_backward(sc, fctx.model.config, dout.to(sc.dt), fctx.st)
-        sc.join_side()
-        sc.grads[PATCH_W] = sc.grads[PATCH_W].view(fctx.wshape)
-        grads = [sc.grads.get(n) for n in fctx.names]
-        fctx.sc = fctx.st = None
+        i = fctx.names.index(PATCH_W)
+        grads = Bk.fn_backward(fctx, dout, lambda sc, d: vit_backward(sc, fctx.model.config, d, fctx.st))
+        grads[i] = grads[i].view(fctx.wshape)
         return (None, None, None, None, *grads)
 
 
@@ -545,6 +469,10 @@ class MPNetModel(Bk.CachedWeights, nn.Module):
         return EncoderOutput(last_hidden_state=out)
 
 
+MPNET_LAYER = (".attention.attn.o", ".attention.LayerNorm", ".intermediate.dense", ".output.dense",
+               ".output.LayerNorm")  # (as BERT_LAYER)
+
+
 def mpnet_forward(ctx: Bk.StepCtx, cfg: MPNetConfig, ids, mask, bucket):
     B, L = ids.shape
     D, H = cfg.hidden_size, cfg.num_attention_heads
@@ -558,12 +486,7 @@ def mpnet_forward(ctx: Bk.StepCtx, cfg: MPNetConfig, ids, mask, bucket):
     rb = K.rel_bias(bucket, P["encoder.relative_attention_bias.weight"])
     for i in range(cfg.num_hidden_layers):
         p = f"encoder.layer.{i}"
-        qkv = Bk.linear_packed(ctx, x, [p + ".attention.attn.q", p + ".attention.attn.k",
-                                        p + ".attention.attn.v"]).view(B, L, 3 * D)
-        o, _ = K.attn_fwd(qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:], H, key_bias=kb, rel_bias=rb)
-        s1, _ = Bk.linear(ctx, Bk.as2d(o), p + ".attention.attn.o", residual=x)
-        h1, _, _ = Bk.layernorm(ctx, s1, p + ".attention.LayerNorm", eps)
-        f, _ = Bk.linear(ctx, h1, p + ".intermediate.dense", act=K.ACT_GELU)
-        s2, _ = Bk.linear(ctx, f, p + ".output.dense", residual=h1)
-        x, _, _ = Bk.layernorm(ctx, s2, p + ".output.LayerNorm", eps)
+        o, _, _ = Bk.self_attn_fwd(ctx, x, [p + ".attention.attn.q", p + ".attention.attn.k", p + ".attention.attn.v"],
+                                   B, H, keep=False, planes=False, key_bias=kb, rel_bias=rb)
+        x, _, _ = Bk.post_ln_fwd(ctx, x, o, p, MPNET_LAYER, eps, keep=False, planes=False)
     return x.view(B, L, D)
