@@ -475,7 +475,8 @@ int mmfd_axpby(int dtype, int64_t n, float a, const void* x, float b, const void
 /* generic dropout (out = keep ? x/(1-p) : 0), index = element index. */
 int mmfd_dropout(int dtype, int64_t n, const void* x, void* out, float p, const uint64_t* seed,
                  uint64_t salt, mmfd_stream_t stream);
-/* out = dropout(dy) * act'(aux) over n contiguous elements (standalone layers.MLP backward) */
+/* out = dropout(dy) * act'(aux) over n contiguous elements (standalone layers.MLP backward);
+   aux is read for MMFD_ACT_GELU / MMFD_ACT_RELU only and may be NULL for MMFD_ACT_NONE */
 int mmfd_act_bwd(int dtype, int64_t n, const void* dy, const void* aux, int act, float dropout_p,
                  const uint64_t* seed, uint64_t salt, void* out, mmfd_stream_t stream);
 /* seed[0] += 1 (advances the step seed inside a captured graph) */

@@ -405,6 +405,7 @@ extern "C" int mmfd_embed_ln_fwd(int dtype, int64_t B, int64_t L, int64_t D, con
 extern "C" int mmfd_position_ids(int64_t B, int64_t L, const int64_t* input_ids, int64_t padding_idx, int64_t* out,
                                  mmfd_stream_t stream) {
   if (B * L == 0) return 0;
+  MMFD_CHECK_ARG(input_ids && out, "position_ids: null pointer");
   hipLaunchKernelGGL(position_ids_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, B, L,
                      input_ids, padding_idx, out);
   MMFD_CHECK_LAUNCH("position_ids");
@@ -415,6 +416,7 @@ extern "C" int mmfd_rel_bias(int64_t H, int64_t Lq, int64_t Lk, const int32_t* b
                              mmfd_stream_t stream) {
   const int64_t n = H * Lq * Lk;
   if (n == 0) return 0;
+  MMFD_CHECK_ARG(bucket && table && out, "rel_bias: null pointer");
   hipLaunchKernelGGL(rel_bias_kernel, dim3(gridn(n, 256)), dim3(256), 0, (hipStream_t)stream, H, Lq, Lk, bucket, table, out);
   MMFD_CHECK_LAUNCH("rel_bias");
   return 0;
@@ -426,6 +428,7 @@ extern "C" int mmfd_patchify(int dtype, int64_t B, int64_t C, int64_t Hh, int64_
   hipStream_t s = (hipStream_t)stream;
   const int64_t total = B * (Hh / P) * (Ww / P) * C * P;
   if (total == 0) return 0;
+  MMFD_CHECK_ARG(pixels && out, "patchify: null pointer");
   if (P % 4 == 0 && Ww % 4 == 0 && ((uintptr_t)pixels % 16) == 0 && ((uintptr_t)out % 16) == 0) {
     const int64_t vt = total * P / 4;
     if (dtype == MMFD_BF16)
@@ -448,6 +451,7 @@ extern "C" int mmfd_vit_tokens_fwd(int dtype, int64_t B, int64_t NP, int64_t D, 
   hipStream_t s = (hipStream_t)stream;
   const int64_t total = B * (NP + 1) * D;
   if (total == 0) return 0;
+  MMFD_CHECK_ARG(cls && pos && out && (patch || NP == 0), "vit_tokens_fwd: null pointer");
   if (dtype == MMFD_BF16)
     hipLaunchKernelGGL((vit_tokens_fwd_kernel<bf16>), dim3(gridn(total, 256)), dim3(256), 0, s, B, NP, D, (const bf16*)patch, cls, pos, (bf16*)out);
   else
@@ -461,6 +465,8 @@ extern "C" int mmfd_vit_tokens_bwd(int dtype, int64_t B, int64_t NP, int64_t D, 
   (void)workspace; (void)workspace_bytes;
   hipStream_t s = (hipStream_t)stream;
   const int64_t total = B * NP * D;
+  if ((NP + 1) * D == 0) return 0;
+  MMFD_CHECK_ARG(dcls && dpos && (dout || B == 0), "vit_tokens_bwd: null pointer");
   if (dtype == MMFD_BF16) {
     if (dpatch) hipLaunchKernelGGL((vit_tokens_dpatch_kernel<bf16>), dim3(gridn(total, 256)), dim3(256), 0, s, B, NP, D, (const bf16*)dout, (bf16*)dpatch);
     hipLaunchKernelGGL((vit_tokens_dpos_kernel<bf16>), dim3(gridn((NP + 1) * D, 256)), dim3(256), 0, s, B, NP, D, (const bf16*)dout, dcls, dpos);

@@ -78,9 +78,11 @@ __global__ void act_bwd_kernel(int64_t n, int64_t width, const T* __restrict__ d
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     float z = to_f32(dy[i]);
     if (p > 0.f) z = (mmfd_hash(seed, salt, (uint64_t)i) < thr) ? 0.f : z * sc;
-    const float a = to_f32(aux[i]);
-    if (act == MMFD_ACT_GELU) z *= gelu_grad_f(a);
-    else if (act == MMFD_ACT_RELU) z = a > 0.f ? z : 0.f;
+    if (act != MMFD_ACT_NONE) {  // aux may be null without an activation
+      const float a = to_f32(aux[i]);
+      if (act == MMFD_ACT_GELU) z *= gelu_grad_f(a);
+      else z = a > 0.f ? z : 0.f;
+    }
     out[i] = from_f32<T>(z);
   }
 }
@@ -162,6 +164,7 @@ extern "C" int mmfd_axpby(int dtype, int64_t n, float a, const void* x, float b,
                           mmfd_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
   if (n == 0) return 0;
+  MMFD_CHECK_ARG(x && out, "mmfd_axpby: null pointer");
   if (dtype == MMFD_BF16)
     hipLaunchKernelGGL((axpby_kernel<bf16>), dim3(grid_for(n, 256)), dim3(256), 0, s, n, a, (const bf16*)x, b, (const bf16*)y, (bf16*)out);
   else if (dtype == MMFD_F32)
@@ -176,6 +179,7 @@ extern "C" int mmfd_dropout(int dtype, int64_t n, const void* x, void* out, floa
   hipStream_t s = (hipStream_t)stream;
   MMFD_CHECK_ARG(p >= 0.f && p < 1.f && seed, "mmfd_dropout: bad p/seed");
   if (n == 0) return 0;
+  MMFD_CHECK_ARG(x && out, "mmfd_dropout: null pointer");
   const uint32_t thr = mmfd_drop_threshold(p);
   if (dtype == MMFD_BF16)
     hipLaunchKernelGGL((dropout_kernel<bf16>), dim3(grid_for(n, 256)), dim3(256), 0, s, n, (const bf16*)x, (bf16*)out, p, thr, seed, salt);
@@ -191,6 +195,8 @@ extern "C" int mmfd_act_bwd(int dtype, int64_t n, const void* dy, const void* au
   MMFD_CHECK_ARG(act == MMFD_ACT_GELU || act == MMFD_ACT_RELU || act == MMFD_ACT_NONE, "act_bwd: bad act");
   MMFD_CHECK_ARG(dropout_p <= 0.f || seed, "act_bwd: dropout needs seed");
   if (n == 0) return 0;
+  MMFD_CHECK_ARG(dy && out, "act_bwd: null pointer");
+  MMFD_CHECK_ARG(aux || act == MMFD_ACT_NONE, "act_bwd: GELU / RELU need aux");
   const float p = dropout_p > 0.f ? dropout_p : 0.f;
   const uint32_t thr = mmfd_drop_threshold(p);
   if (dtype == MMFD_BF16)

@@ -284,14 +284,26 @@ void xent(at::TensorList logits, at::IntArrayRef cols, const at::Tensor& labels,
   std::vector<const float*> lp(n);
   std::vector<float*> dp(n);
   std::vector<int> cp(n);
+  TORCH_CHECK(logits[0].dim() == 2, "mmfd::xent: logits must be [B, C], got ", logits[0].sizes());
+  const int64_t B = logits[0].size(0), C = logits[0].size(1);
   for (int i = 0; i < n; ++i) {
     TORCH_CHECK(logits[i].scalar_type() == at::kFloat && logits[i].is_contiguous(), "mmfd::xent: contiguous fp32 logits");
+    TORCH_CHECK(logits[i].dim() == 2 && logits[i].size(0) == B && logits[i].size(1) == C, "mmfd::xent: logits of path ", i,
+                " are ", logits[i].sizes(), ", path 0 has [", B, ", ", C, "]");
     lp[i] = logits[i].data_ptr<float>();
     cp[i] = (int)cols[i];
-    if (!dlogits.empty()) dp[i] = dlogits[i].data_ptr<float>();
+    if (!dlogits.empty()) {
+      TORCH_CHECK(dlogits[i].scalar_type() == at::kFloat && dlogits[i].is_contiguous() &&
+                  dlogits[i].sizes() == logits[i].sizes(), "mmfd::xent: dlogits of path ", i,
+                  " must be contiguous fp32 ", logits[i].sizes());
+      dp[i] = dlogits[i].data_ptr<float>();
+    }
   }
+  TORCH_CHECK(labels.scalar_type() == at::kLong && labels.dim() >= 1 && labels.dim() <= 2 && labels.size(0) == B,
+              "mmfd::xent: labels must be int64 with ", B, " rows, got ", labels.scalar_type(), " ", labels.sizes());
+  TORCH_CHECK(labels.dim() == 1 || labels.stride(1) == 1, "mmfd::xent: label columns must be contiguous");
   const int64_t ld = labels.dim() > 1 ? labels.stride(0) : 1;
-  check(mmfd_xent_fwd_bwd(n, logits[0].size(0), logits[0].size(1), lp.data(), cp.data(), labels.data_ptr<int64_t>(),
+  check(mmfd_xent_fwd_bwd(n, B, C, lp.data(), cp.data(), labels.data_ptr<int64_t>(),
                           ld, loss.data_ptr<float>(), (int)loss.numel(), dlogits.empty() ? nullptr : dp.data(),
                           ptr_or_null<const float>(dloss_scale), stream_of(loss)), "mmfd::xent");
 }

@@ -953,8 +953,9 @@ def axpby(a, x, b=0.0, y=None, out=None):
 
 def dropout(x, p, seed, salt, out=None):
     out = out if out is not None else torch.empty_like(x)
-    _check(lib().mmfd_dropout(dtype_code(x.dtype), x.numel(), _ptr(x), _ptr(out), float(p), seed.ptr(),
-                              int(salt) & 0xFFFFFFFFFFFFFFFF, _stream()), "mmfd_dropout")
+    _check(lib().mmfd_dropout(dtype_code(x.dtype), x.numel(), _ptr(x), _ptr(out), float(p),
+                              seed.ptr() if seed is not None else None, int(salt) & 0xFFFFFFFFFFFFFFFF, _stream()),
+           "mmfd_dropout")
     return out
 
 

@@ -63,7 +63,7 @@ class _LinearFn(torch.autograd.Function):
         dy2 = dy.reshape(-1, dy.shape[-1]).contiguous().to(x2.dtype)
         if act or p > 0:
             # the epilogue applied dropout after the activation: one elementwise kernel undoes both
-            dy2 = K.act_bwd(dy2, aux if act else dy2, K.ACT_GELU if act else K.ACT_NONE, dropout_p=p, seed=seed,
+            dy2 = K.act_bwd(dy2, aux if act else None, K.ACT_GELU if act else K.ACT_NONE, dropout_p=p, seed=seed,
                             salt=K.salt_of(site))
         dx = K.gemm(dy2, wc, trans_b=True).reshape(shp) if ctx.needs_input_grad[0] else None
         db = torch.empty(dy2.shape[1], device=dy2.device, dtype=torch.float32) if has_b else None
