@@ -119,7 +119,7 @@ __host__ __device__ __forceinline__ uint32_t mmfd_hash_k(uint32_t key, uint64_t 
 __host__ __device__ __forceinline__ uint32_t mmfd_hash(uint64_t seed, uint64_t salt, uint64_t idx) {
   return mmfd_hash_k(mmfd_hash_key(seed, salt), idx);
 }
-// 16-bit threshold of the attention kernels' pair hashes (attention.hip pair_keep): keep <=> the
+// 16-bit threshold of the attention kernels' pair hashes (attn_common.h pair_keep): keep <=> the
 // element's 16-bit half >= thr16 = round(p * 65536); 65536 drops everything
 __host__ __device__ __forceinline__ uint32_t mmfd_drop_threshold16(float p) {
   const double t = (double)p * 65536.0 + 0.5;

@@ -70,7 +70,7 @@ def drop_threshold16(p: float) -> int:
 
 def attn_keep_mask(seed: int, salt: int, shape, p: float, rows=None):
     """Keep-mask of attention probabilities [B, H, Lq, Lk] as the attention kernels draw it
-    (multimodal-misinformation-detection_amd/csrc/attention.hip pair_keep): ONE hash per key pair,
+    (multimodal-misinformation-detection_amd/csrc/attn_common.h pair_keep): ONE hash per key pair,
     h = hash(row * kp + k // 2) with row = (b*H + h)*Lq + q and kp = ceil(Lk / 2); element (row, k) is
     kept when its 16-bit half (low for even k, high for odd k) >= round(p * 65536). `rows`: the
     whole-batch indices of the tensor's batch rows (chunked oracle steps; default arange(B))."""

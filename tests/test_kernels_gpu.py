@@ -477,8 +477,10 @@ def _attn_ref(q, k, v, H, scale, key_bias=None, keep=None, p=0.0):
 
 ATTN_CASES = [(2, 4, 128, 128, 64), (2, 8, 197, 197, 32), (3, 2, 13, 29, 64), (2, 8, 128, 197, 32),
               (1, 12, 70, 70, 64), (2, 4, 21, 33, 8), (2, 2, 40, 40, 16), (1, 3, 65, 130, 48),
-              (1, 2, 260, 300, 64), (2, 16, 256, 256, 64),  # L > 256: streaming backward kernels
-              (1, 2, 512, 512, 64),  # bf16 forward keeps up to 512 keys resident
+              # the kernels these reach are pinned in tests/golden/attn_plans.json (test_attn_plan_cpu.py):
+              (1, 2, 260, 300, 64),  # L > 256: the streaming kernels, forward and backward
+              (2, 16, 256, 256, 64),  # the resident kernels at their limit
+              (1, 2, 512, 512, 64),  # streaming again: 512 keys stay resident (bf16 forward) only from B*H = 256
               (2, 4, 197, 197, 64), (1, 2, 208, 208, 64)]  # 13 query blocks: the last one split over two waves
 
 
