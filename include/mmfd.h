@@ -214,8 +214,9 @@ typedef struct mmfd_attn_args {
                                       [nW][H][L][L] shift masks, batch = images x nW windows) */
   const float* cos_logit_scale;    /* forward only, NULL = plain attention. Otherwise Swinv2 cosine
                                       attention: q_h, k_h are L2-normalised (eps 1e-12) and q_h scaled
-                                      by exp(min(cos_logit_scale[h], cos_max_log)) while staged (bf16,
-                                      Lk <= 256, rel_bias required); replaces mmfd_swin_qk_norm */
+                                      by exp(min(cos_logit_scale[h], cos_max_log)), applied to the fp32
+                                      scores of the raw q_h . k_h (bf16, resident forward, rel_bias
+                                      required); replaces mmfd_swin_qk_norm */
   float cos_max_log;
   /* backward, fp32 only: bf16 split planes [3][B*Lq][3*H*D] (mmfd_split3 form) of the packed
      gradient [dq | dk | dv] — dq, dk, dv must be the three column blocks of one contiguous

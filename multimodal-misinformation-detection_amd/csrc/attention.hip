@@ -228,8 +228,9 @@ void plan_kernels(Plan& pl, AttnP& p, const mmfd_attn_args& a, bool bwd) {
     const int hpb = p.Lk <= 64 && p.Lq <= 32 ? 4 : p.Lk <= 64 && p.Lq <= 64 ? 2 : 1;
     const int lmax = hpb > 1 ? 64 : sizeof(T) == 2 ? V2_LMAX_FWD : V2_LMAX;
     pl.add(hpb == 4 ? fwd_v2_kern<T, D, 4>(p) : hpb == 2 ? fwd_v2_kern<T, D, 2>(p) : fwd_v2_kern<T, D, 1>(p),
-           dim3((unsigned)((nbh + hpb - 1) / hpb)), V2_THREADS, v2_fwd_lds<T, D>(hpb, v2_pad(p.Lk, v2_kc<T>())),
-           v2_fwd_lds<T, D>(hpb, lmax), what);
+           dim3((unsigned)((nbh + hpb - 1) / hpb)), V2_THREADS,
+           v2_fwd_lds<T, D>(hpb, v2_pad(p.Lk, v2_kc<T>())) + (p.cos_ls ? v2_fwd_cos_lds(hpb, v2_pad(p.Lk, v2_kc<T>())) : 0),
+           v2_fwd_lds<T, D>(hpb, lmax) + v2_fwd_cos_lds(hpb, lmax), what);
   } else if (pl.family == RESIDENT) {
     const int mode = v2_mode(p);
     if (p.rel_bias) add_bwd_v2<T, D, true, 0>(pl, p, what);

@@ -86,11 +86,13 @@ __device__ __forceinline__ void stage_two(char* lds_a, const T* __restrict__ bas
   }
 }
 
-// K rows staged as k / max(|k|, 1e-12) (Swinv2 cosine attention): the NCH chunks of a row belong to
-// NCH consecutive lanes, so the row's sum of squares is a butterfly over those lanes
+// K rows staged as they are, and 1 / max(|k|, 1e-12) of each row into kinv (Swinv2 cosine attention:
+// the norms scale the fp32 scores, so the MFMA operands stay the exact inputs — normalised rows rounded
+// to bf16 cost up to 2^-8 of the logit scale per logit, 0.4 at the clamp of 100): the NCH chunks of a
+// row belong to NCH consecutive lanes, so the row's sum of squares is a butterfly over those lanes
 template <int D, int NTH>
-__device__ __forceinline__ void stage_rows_cos(char* lds, const bf16* __restrict__ base, int64_t st, int64_t nrows,
-                                               int nrows_pad, int tid, int dreal) {
+__device__ __forceinline__ void stage_rows_cos(char* lds, float* kinv, const bf16* __restrict__ base, int64_t st,
+                                               int64_t nrows, int nrows_pad, int tid, int dreal) {
   constexpr int NCH = AT<bf16, D>::NCH, EPC = AT<bf16, D>::EPC;
   for (int c = tid; c < nrows_pad * NCH; c += NTH) {
     const int r = c / NCH, ch = c % NCH;
@@ -102,37 +104,26 @@ __device__ __forceinline__ void stage_rows_cos(char* lds, const bf16* __restrict
     for (int e = 0; e < EPC; ++e) { f[e] = (float)x[e]; ss = fmaf(f[e], f[e], ss); }
 #pragma unroll
     for (int o = 1; o < NCH; o <<= 1) ss += __shfl_xor(ss, o, 64);
-    const float inv = 1.f / fmaxf(sqrtf(ss), 1e-12f);
-    bf16x8 y;
-#pragma unroll
-    for (int e = 0; e < EPC; ++e) y[e] = (bf16)(f[e] * inv);
-    *reinterpret_cast<uint4*>(lds + row_off<bf16, D>(r, ch)) = __builtin_bit_cast(uint4, y);
+    if (ch == 0) kinv[r] = 1.f / fmaxf(sqrtf(ss), 1e-12f);
+    *reinterpret_cast<uint4*>(lds + row_off<bf16, D>(r, ch)) = v;
   }
 }
 
-// q fragments (load_row_regs layout: a row's chunks sit in lanes li, li+16, li+32, li+48) scaled to
-// q / max(|q|, 1e-12) * mult, rounded as the separate normalisation pass would
+// mult / max(|q|, 1e-12) of the lane's query row from its q fragments (load_row_regs layout: a row's
+// chunks sit in lanes li, li+16, li+32, li+48; lane (g, li) owns the scores of query li)
 template <int D>
-__device__ __forceinline__ void cos_norm_q(uint4* f, float mult) {
+__device__ __forceinline__ float cos_q_scale(const uint4* f, float mult) {
   constexpr int KCH = AT<bf16, D>::KCH;
   float ss = 0.f;
-  float v[KCH][8];
 #pragma unroll
   for (int kc = 0; kc < KCH; ++kc) {
     const bf16x8 x = __builtin_bit_cast(bf16x8, f[kc]);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { v[kc][e] = (float)x[e]; ss = fmaf(v[kc][e], v[kc][e], ss); }
+    for (int e = 0; e < 8; ++e) { const float v = (float)x[e]; ss = fmaf(v, v, ss); }
   }
   ss += __shfl_xor(ss, 16, 64);
   ss += __shfl_xor(ss, 32, 64);
-  const float inv = 1.f / fmaxf(sqrtf(ss), 1e-12f);
-#pragma unroll
-  for (int kc = 0; kc < KCH; ++kc) {
-    bf16x8 y;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) y[e] = (bf16)((v[kc][e] * inv) * mult);
-    f[kc] = __builtin_bit_cast(uint4, y);
-  }
+  return mult / fmaxf(sqrtf(ss), 1e-12f);
 }
 
 constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
@@ -172,13 +163,15 @@ __device__ __forceinline__ void stage_kbias(float* dst, const AttnP& p, int64_t 
 }
 
 // Dynamic LDS of the three kernels, as each carves its smem (rows padded to the MFMA k-chunk):
-//   forward: per head of the workgroup, the K and V images and the per-key bias floats
+//   forward: per head of the workgroup, the K and V images and the per-key bias floats; cosine attention
+//            adds, behind all of them, the per-key inverse norms (v2_fwd_cos_lds)
 //   dQ     : K and V row images, K transposed unless DUAL, the per-key bias floats
 //   dK/dV  : Q and dO as row and (unless DUAL) transposed images; lse, delta and key bias at V2_LMAX
 //            floats each; dm_words keep-bitmask words per query row when AttnP::dm_lds
 template <typename T, int D> constexpr int v2_fwd_lds(int hpb, int lk_pad) {
   return hpb * (2 * lk_pad * AT<T, D>::RB + lk_pad * 4);
 }
+constexpr int v2_fwd_cos_lds(int hpb, int lk_pad) { return hpb * lk_pad * 4; }
 template <typename T, int D> constexpr int v2_dq_lds(int lk_pad) {
   return (V2<T, D>::DUAL ? 2 : 3) * lk_pad * AT<T, D>::RB + lk_pad * 4;
 }
@@ -217,6 +210,8 @@ __global__ void __launch_bounds__(V2_THREADS, sizeof(T) == 2 && !REL ? 4 : 1) at
   char* k_img = hbase;
   char* v_img = hbase + lk_pad * C::RB;
   float* kbias = reinterpret_cast<float*>(hbase + 2 * lk_pad * C::RB);
+  // cosine only (the launch adds v2_fwd_cos_lds): 1 / |k| per key, behind every head's images
+  float* kinv = reinterpret_cast<float*>(smem + v2_fwd_lds<T, D>(HPB, lk_pad)) + sub * lk_pad;
   const T* qb = reinterpret_cast<const T*>(p.q) + b * p.q_sb + h * p.D;
   const T* kb_g = reinterpret_cast<const T*>(p.k) + b * p.k_sb + h * p.D;
   const int nqb = (int)((p.Lq + 15) / 16);
@@ -225,7 +220,7 @@ __global__ void __launch_bounds__(V2_THREADS, sizeof(T) == 2 && !REL ? 4 : 1) at
   bool cosine = false;
   if constexpr (sizeof(T) == 2) {
     cosine = REL && p.cos_ls != nullptr;
-    if (cosine) stage_rows_cos<D, TPH>(k_img, kb_g, p.k_st, p.Lk, lk_pad, htid, p.D);
+    if (cosine) stage_rows_cos<D, TPH>(k_img, kinv, kb_g, p.k_st, p.Lk, lk_pad, htid, p.D);
   }
   const T* vb_g = reinterpret_cast<const T*>(p.v) + b * p.v_sb + h * p.D;
   if (!cosine)
@@ -249,8 +244,9 @@ __global__ void __launch_bounds__(V2_THREADS, sizeof(T) == 2 && !REL ? 4 : 1) at
 #pragma unroll
     for (int kc = 0; kc < C::KCH; ++kc) qf[kc] = qn[kc];
     load_row_regs<T, D>(qn, qb, p.q_st, q0 + WPH * 16 + li, p.Lq, lane, p.D);
+    float qscale = 1.f;  // cosine: exp(logit scale) / |q| of this lane's query
     if constexpr (sizeof(T) == 2) {
-      if (cosine) cos_norm_q<D>(qf, qmult);
+      if (cosine) qscale = cos_q_scale<D>(qf, qmult);
     }
     const uint64_t hrow = (uint64_t)(bh * p.Lq + myq) * (uint64_t)p.kp;  // pair-index base of this query row
     const uint32_t rowc1 = ((uint32_t)hrow + (uint32_t)(2 * g)) * HASH_C1;
@@ -312,6 +308,12 @@ __global__ void __launch_bounds__(V2_THREADS, sizeof(T) == 2 && !REL ? 4 : 1) at
         const float kb[4] = {kb4.x, kb4.y, kb4.z, kb4.w};
         float rb[4] = {0.f, 0.f, 0.f, 0.f};
         const int kk = k0 + ks * 16 + 4 * g;
+        if constexpr (REL && sizeof(T) == 2) {
+          if (cosine) {  // the scores of raw q . k become cosines times the logit scale
+            const float4 ki = *reinterpret_cast<const float4*>(kinv + kk);
+            s[ks][0] *= qscale * ki.x; s[ks][1] *= qscale * ki.y; s[ks][2] *= qscale * ki.z; s[ks][3] *= qscale * ki.w;
+          }
+        }
         if (REL) {  // the 4 keys of a lane are contiguous: one 16-B load per subtile when aligned
           if (rel4) {
             if (kk < p.Lk) {
