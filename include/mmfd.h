@@ -424,7 +424,7 @@ int mmfd_vit_tokens_bwd(int dtype, int64_t B, int64_t NP, int64_t D, const void*
 /* ------------------------------------------------------------------------------------------- */
 /* Swinv2 image encoder (reference default image encoder: Swinv2Model swinv2-base-patch4-window8- */
 /* 256, train.py:332, called at train.py:142-143 / preprocess_embeddings.py:91-92; transformers  */
-/* modeling_swinv2.py). Inference only.                                                        */
+/* modeling_swinv2.py). Inference entry points first, then the fine-tuning adjoints.           */
 /* ------------------------------------------------------------------------------------------- */
 /* dst row (b, r) = concat_g src row (b, idx[r*G + g]); rows are row_bytes wide (multiple of 16).
  * Replaces torch.roll + window_partition / window_reverse and the patch-merging 2x2 concat. */
@@ -442,6 +442,50 @@ int mmfd_swin_bias(int64_t nW, int64_t H, int64_t L, const float* table, const i
  * q_h /= max(|q_h|, 1e-12) and *= exp(min(logit_scale[h], max_log)); k_h /= max(|k_h|, 1e-12) */
 int mmfd_swin_qk_norm(int dtype, int64_t rows, int64_t H, int64_t d, void* qkv, int64_t ld,
                       const float* logit_scale, float max_log, mmfd_stream_t stream);
+
+/* ---- Swinv2 fine-tuning (Swinv2Config(trainable=True); the reference loads the encoder with
+ * requires_grad left on unless --freeze_image, train.py:332-340, and backpropagates through
+ * modeling_swinv2.py Swinv2SelfAttention.forward). Under grad a block runs mmfd_swin_qk_norm_train and
+ * then plain mmfd_attn_fwd / mmfd_attn_bwd (scale 1, the block's bias); the entry points below are
+ * the adjoints those do not have. All deterministic: no floating-point atomics, fixed summation order. */
+/* mmfd_swin_qk_norm (the same bits on q and k, v untouched) that also writes the inverse norms
+ * inv_norm[row][0 = q | 1 = k][h] = 1 / max(|.|, 1e-12), fp32 (F.normalize in
+ * Swinv2SelfAttention.forward, kept for its backward); d = 32 or 64, as the backward */
+int mmfd_swin_qk_norm_train(int dtype, int64_t rows, int64_t H, int64_t d, void* qkv, int64_t ld,
+                            const float* logit_scale, float max_log, float* inv_norm, mmfd_stream_t stream);
+/* The adjoint of the cosine pass (autograd of F.normalize(q) * exp(clamp(logit_scale, max=max_log)) in
+ * Swinv2SelfAttention.forward), in place on the q and k thirds of the packed gradient rows dqkv
+ * [rows][ldg] (the v third stays). qkv_norm [rows][ldn]: the operands mmfd_swin_qk_norm_train left;
+ * with qh = q/|q|, s = exp(min(ls_h, max_log)), qn = s qh and g = dL/dqn:
+ *   dq = (s/|q|) (g - qh (qh . g)) for |q| >= 1e-12, else (s/1e-12) g;  k the same with s = 1;
+ *   d_logit_scale[h] = sum_rows g . qn for ls_h <= max_log, else exactly 0 (torch.clamp).
+ * The logit-scale sum goes through per-block partials (workspace >=
+ * mmfd_swin_qk_norm_bwd_workspace_bytes(rows, H)) added in a fixed order. d = 32 or 64, H <= 256. */
+int64_t mmfd_swin_qk_norm_bwd_workspace_bytes(int64_t rows, int64_t H);
+int mmfd_swin_qk_norm_bwd(int dtype, int64_t rows, int64_t H, int64_t d, void* dqkv, int64_t ldg,
+                          const void* qkv_norm, int64_t ldn, const float* inv_norm, const float* logit_scale,
+                          float max_log, float* d_logit_scale, void* workspace, int64_t workspace_bytes,
+                          mmfd_stream_t stream);
+/* The gradient of a rel_bias that several batch rows share (autograd's sum over the window batch of
+ * relative_position_bias / the shift mask's rows in Swinv2SelfAttention.forward):
+ *   d_bias[m][h][i][j] = sum_{b = m (mod M)} P (dP - delta),   fp32 [M][H][Lq][Lk], written once,
+ * M = 1 for a bias shared by the batch (rel_bias_sb = 0) and M = rel_bias_mod otherwise (M == B is a
+ * modulo bias like any other: one term per row). `args` are the arguments the preceding mmfd_attn_bwd
+ * call took: delta holds what that call left, dq / dk / dv are not touched. Refused on the host, before any launch: a per-batch bias (that is
+ * mmfd_attn_args.d_rel_bias), attention dropout, cosine attention, Lq or Lk > 256. */
+int mmfd_attn_bwd_bias_sum(const mmfd_attn_args* args, float* d_bias, mmfd_stream_t stream);
+/* The adjoint of mmfd_swin_bias: d_table[r][h] = 16 sg (1 - sg) sum_w sum_{(i,j): rpi[i*L+j] == r}
+ * d_bias[w][h][i][j] with sg = sigmoid(table[r][h]); d_bias fp32 [nW][H][L][L], table / d_table fp32
+ * [T][H] (16 * sigmoid(relative_position_bias_table[index]) in Swinv2SelfAttention.forward; the shift
+ * mask is a constant and takes no gradient) */
+int mmfd_swin_bias_bwd(int64_t nW, int64_t H, int64_t L, int64_t T, const float* d_bias, const float* table,
+                       const int32_t* rpi, float* d_table, mmfd_stream_t stream);
+/* The adjoint of mmfd_swin_cpb (continuous_position_bias_mlp: Linear(2, 512) - ReLU - Linear(512, H, no
+ * bias)): d_w1 [512][2], d_b1 [512], d_w2 [H][512] from d_table [T][H]; the hidden values are recomputed
+ * (relu'(0) = 0 as torch); H <= 32 */
+int mmfd_swin_cpb_bwd(int64_t T, int64_t H, const float* coords, const float* w1, const float* b1,
+                      const float* w2, const float* d_table, float* d_w1, float* d_b1, float* d_w2,
+                      mmfd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------- */
 /* AdamW (torch.optim.AdamW defaults as used at train.py:356/188), multi-tensor, one launch.    */

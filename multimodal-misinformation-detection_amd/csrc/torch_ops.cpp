@@ -197,7 +197,8 @@ void attn_bwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, con
               int64_t rel_bias_mod, double dropout_p, const std::optional<at::Tensor>& seed, int64_t salt,
               bool accumulate_dq, bool accumulate_dkv, const std::optional<at::Tensor>& dqkv_planes = std::nullopt,
               bool planes_only = false, const std::optional<at::Tensor>& drop_mask = std::nullopt,
-              const std::optional<at::Tensor>& d_rel_bias = std::nullopt) {
+              const std::optional<at::Tensor>& d_rel_bias = std::nullopt,
+              const std::optional<at::Tensor>& delta_out = std::nullopt) {
   mmfd_attn_args a = attn_args(q, k, v, heads, scale, key_bias, rel_bias, rel_bias_sb, rel_bias_mod, dropout_p, seed, salt);
   const void* p;
   head_view(o, "o", &p, &a.o_sb, &a.o_st); a.o = const_cast<void*>(p);
@@ -212,7 +213,16 @@ void attn_bwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, con
   head_view(dq, "dq", &p, &a.dq_sb, &a.dq_st); a.dq = const_cast<void*>(p);
   head_view(dk, "dk", &p, &a.dk_sb, &a.dk_st); a.dk = const_cast<void*>(p);
   head_view(dv, "dv", &p, &a.dv_sb, &a.dv_st); a.dv = const_cast<void*>(p);
-  at::Tensor delta = at::empty({a.B, a.H, a.Lq}, q.options().dtype(at::kFloat));
+  // the delta workspace: the caller's (it keeps rowsum(dO * O) for mmfd_attn_bwd_bias_sum) or a scratch one
+  at::Tensor delta;
+  if (delta_out.has_value() && delta_out->defined()) {
+    TORCH_CHECK(delta_out->scalar_type() == at::kFloat && delta_out->is_contiguous() && delta_out->is_cuda() &&
+                    delta_out->numel() == a.B * a.H * a.Lq,
+                "mmfd::attn_bwd: delta must be a contiguous fp32 device tensor [B, H, Lq]");
+    delta = *delta_out;
+  } else {
+    delta = at::empty({a.B, a.H, a.Lq}, q.options().dtype(at::kFloat));
+  }
   a.delta = delta.data_ptr<float>();
   a.accumulate_dq = accumulate_dq; a.accumulate_dkv = accumulate_dkv;
   if (dqkv_planes.has_value() && dqkv_planes->defined()) {
@@ -364,7 +374,7 @@ TORCH_LIBRARY(mmfd, m) {
         "Tensor(c!) dv, int heads, float scale, Tensor? key_bias, Tensor? rel_bias, int rel_bias_sb, int rel_bias_mod, "
         "float dropout_p, Tensor? seed, int salt, bool accumulate_dq, bool accumulate_dkv, "
         "Tensor(d!)? dqkv_planes=None, bool planes_only=False, Tensor? drop_mask=None, "
-        "Tensor(e!)? d_rel_bias=None) -> ()");
+        "Tensor(e!)? d_rel_bias=None, Tensor(f!)? delta=None) -> ()");
   m.def("layernorm_fwd(Tensor x, Tensor gamma, Tensor beta, float eps, Tensor(a!) y, Tensor(b!) mean, "
         "Tensor(c!) rstd, Tensor(d!)? planes=None) -> ()");
   m.def("layernorm_bwd(Tensor dy, Tensor x, Tensor gamma, Tensor mean, Tensor rstd, Tensor(a!) dx, Tensor? dx_add, "

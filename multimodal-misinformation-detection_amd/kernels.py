@@ -199,6 +199,12 @@ SIGNATURES = {
     "mmfd_swin_cpb": (_I, [_I64, _I64, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mmfd_swin_bias": (_I, [_I64, _I64, _I64, _VP, _VP, _VP, _VP, _VP]),
     "mmfd_swin_qk_norm": (_I, [_I, _I64, _I64, _I64, _VP, _I64, _VP, _F, _VP]),
+    "mmfd_swin_qk_norm_train": (_I, [_I, _I64, _I64, _I64, _VP, _I64, _VP, _F, _VP, _VP]),
+    "mmfd_swin_qk_norm_bwd_workspace_bytes": (_I64, [_I64, _I64]),
+    "mmfd_swin_qk_norm_bwd": (_I, [_I, _I64, _I64, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _F, _VP, _VP, _I64, _VP]),
+    "mmfd_attn_bwd_bias_sum": (_I, [ctypes.POINTER(AttnArgs), _VP, _VP]),
+    "mmfd_swin_bias_bwd": (_I, [_I64, _I64, _I64, _I64, _VP, _VP, _VP, _VP, _VP]),
+    "mmfd_swin_cpb_bwd": (_I, [_I64, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
 }
 
 _lib = None
@@ -798,12 +804,14 @@ def attn_fill_masked_rows(v, o, H, mask):
 
 def attn_bwd(q, k, v, o, lse, dout, H, *, dq=None, dk=None, dv=None, scale=None, key_bias=None, rel_bias=None,
              dropout_p=0.0, seed=None, salt=0, accumulate_dq=False, accumulate_dkv=False, dqkv_planes=None,
-             planes_only=False, drop_mask=None, d_rel_bias=None):
+             planes_only=False, drop_mask=None, d_rel_bias=None, delta=None):
     """dq, dk, dv (views of one packed [B, L, 3*H*D] buffer when `dqkv_planes` is given: bf16
     [3, B*L, 3*H*D] split planes of that buffer, written by the kernels; planes_only skips the
     fp32 stores — for a gradient read only by split-operand GEMMs, see x6_ok).
     `d_rel_bias` (contiguous fp32 [B, H, Lq, Lk]): receives the gradient with respect to a per-batch
-    `rel_bias` [B, H, Lq, Lk] (no dropout; include/mmfd.h mmfd_attn_args.d_rel_bias)."""
+    `rel_bias` [B, H, Lq, Lk] (no dropout; include/mmfd.h mmfd_attn_args.d_rel_bias).
+    `delta` (contiguous fp32 [B, H, Lq]): the call's delta workspace, kept by the caller — it holds
+    rowsum(dO * O) afterwards, which attn_bwd_bias_sum reads."""
     _require_cuda(q, k, v, o, lse, dout)
     B, Lq, HD = q.shape
     Lk = k.shape[1]
@@ -817,8 +825,63 @@ def attn_bwd(q, k, v, o, lse, dout, H, *, dq=None, dk=None, dv=None, scale=None,
     _ops().attn_bwd(q, k, v, o, lse, dout, dq, dk, dv, int(H), float(scale if scale is not None else D ** -0.5),
                     key_bias, rel_bias if rb is not None else None, int(rb_sb), int(rb_mod), float(dropout_p),
                     seed.t if seed is not None else None, _salt(salt), bool(accumulate_dq), bool(accumulate_dkv),
-                    dqkv_planes, bool(planes_only), drop_mask if dropout_p > 0 else None, d_rel_bias)
+                    dqkv_planes, bool(planes_only), drop_mask if dropout_p > 0 else None, d_rel_bias, delta)
     return dq, dk, dv
+
+
+def attn_bwd_bias_sum(q, k, v, o, lse, dout, H, delta, *, rel_bias, rel_bias_mod=None, scale=None, key_bias=None,
+                      dropout_p=0.0, cos_logit_scale=None, out=None):
+    """The gradient of a `rel_bias` shared by the batch ([H, Lq, Lk]) or read with a batch modulus
+    ([M, H, Lq, Lk], B % M == 0): fp32 [M, H, Lq, Lk] (M = 1 for the shared form) = the sum over the batch
+    rows b = m (mod M) of P (dP - delta). The arguments are those of the preceding attn_bwd call, `delta`
+    the tensor that call was given (include/mmfd.h mmfd_attn_bwd_bias_sum; Lq, Lk <= 256; a per-batch
+    bias, dropout and cosine attention are refused). A [B, H, Lq, Lk] bias reads as per-batch, as in
+    attn_fwd / attn_bwd (the same numbers either way there); a caller whose modulo bias can have M == B
+    (Swinv2 with one image: the batch is its nW windows) says so with `rel_bias_mod` = M, and gets the
+    M-row sum of one term each."""
+    _require_cuda(q, k, v, o, lse, dout, delta, rel_bias, key_bias)
+    B, Lq, HD = q.shape
+    Lk = k.shape[1]
+    D = HD // H
+    rb, rb_sb, rb_mod = _rel_bias_args(rel_bias, B, H, Lq, Lk)
+    if rb is None:
+        raise ValueError("attn_bwd_bias_sum: no rel_bias")
+    if rel_bias_mod is not None:
+        if tuple(rel_bias.shape) != (rel_bias_mod, H, Lq, Lk) or B % rel_bias_mod:
+            raise ValueError(f"attn_bwd_bias_sum: rel_bias_mod = {rel_bias_mod} needs a [{rel_bias_mod}, H, Lq, Lk] "
+                             f"bias and B % {rel_bias_mod} == 0, got {tuple(rel_bias.shape)} with B = {B}")
+        rb_sb, rb_mod = H * Lq * Lk, int(rel_bias_mod)
+    if delta.dtype != torch.float32 or not delta.is_contiguous() or delta.numel() != B * H * Lq:
+        raise ValueError("attn_bwd_bias_sum: delta must be the contiguous fp32 [B, H, Lq] tensor attn_bwd filled")
+    if lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() != B * H * Lq:
+        raise ValueError("attn_bwd_bias_sum: lse must be contiguous fp32 [B, H, Lq]")
+    if key_bias is not None and (key_bias.dtype != torch.float32 or not key_bias.is_contiguous()
+                                 or key_bias.numel() != B * Lk):
+        raise ValueError("attn_bwd_bias_sum: key_bias must be contiguous fp32 [B, Lk]")
+    for t in (k, v, o, dout):
+        if t.dtype != q.dtype:
+            raise TypeError("attn_bwd_bias_sum: q, k, v, o, dout must share a dtype")
+    M = rb_mod if rb_mod else (B if rb_sb else 1)  # (a per-batch bias: the library refuses it)
+    if out is None:
+        out = torch.empty((M, H, Lq, Lk), device=q.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (M, H, Lq, Lk):
+        raise ValueError(f"attn_bwd_bias_sum: out must be contiguous fp32 {(M, H, Lq, Lk)}")
+    a = AttnArgs()
+    a.dtype = dtype_code(q.dtype)
+    a.B, a.H, a.Lq, a.Lk, a.D = B, H, Lq, Lk, D
+    a.scale = float(scale if scale is not None else D ** -0.5)
+    a.q, a.q_sb, a.q_st = _head_view(q, H, D)
+    a.k, a.k_sb, a.k_st = _head_view(k, H, D)
+    a.v, a.v_sb, a.v_st = _head_view(v, H, D)
+    a.o, a.o_sb, a.o_st = _head_view(o, H, D)
+    a.dout, a.do_sb, a.do_st = _head_view(dout, H, D)
+    a.lse, a.delta = lse.data_ptr(), delta.data_ptr()
+    a.key_bias = key_bias.data_ptr() if key_bias is not None else None
+    a.rel_bias, a.rel_bias_sb, a.rel_bias_mod = rb, rb_sb, rb_mod
+    a.dropout_p = float(dropout_p)
+    a.cos_logit_scale = cos_logit_scale.data_ptr() if cos_logit_scale is not None else None
+    _check(lib().mmfd_attn_bwd_bias_sum(ctypes.byref(a), _ptr(out), _stream()), "mmfd_attn_bwd_bias_sum")
+    return out
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1300,3 +1363,70 @@ def swin_qk_norm(qkv, H, d, logit_scale, max_log):
     _check(lib().mmfd_swin_qk_norm(dtype_code(qkv.dtype), qkv.shape[0], H, d, _ptr(qkv), _ld(qkv), _ptr(ls),
                                    float(max_log), _stream()), "mmfd_swin_qk_norm")
     return qkv
+
+
+def _f32c(t, what):
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous fp32 tensor")
+    return t
+
+
+def swin_qk_norm_train(qkv, H, d, logit_scale, max_log):
+    """swin_qk_norm (the same bits) that also returns the inverse norms: (qkv, inv fp32 [rows, 2, H]) with
+    inv[r, 0 | 1, h] = 1 / max(|q_h| | |k_h|, 1e-12) — what swin_qk_norm_bwd reads"""
+    _require_cuda(qkv, logit_scale)
+    ls = _f32c(logit_scale, "logit_scale")
+    if ls.numel() != H or qkv.shape[1] < 3 * H * d:
+        raise ValueError("swin_qk_norm_train: qkv must be packed [rows, 3*H*d] rows and logit_scale hold H values")
+    inv = torch.empty((qkv.shape[0], 2, H), device=qkv.device, dtype=torch.float32)
+    _check(lib().mmfd_swin_qk_norm_train(dtype_code(qkv.dtype), qkv.shape[0], H, d, _ptr(qkv), _ld(qkv), _ptr(ls),
+                                         float(max_log), _ptr(inv), _stream()), "mmfd_swin_qk_norm_train")
+    return qkv, inv
+
+
+def swin_qk_norm_bwd(dqkv, qkv_norm, inv, H, d, logit_scale, max_log):
+    """adjoint of the cosine pass, in place on the q and k thirds of the packed gradient rows `dqkv`
+    [rows, 3*H*d] (`qkv_norm`, `inv`: what swin_qk_norm_train left); returns (dqkv, d_logit_scale fp32 [H]),
+    the latter exactly 0 for heads whose logit scale is past the clamp"""
+    _require_cuda(dqkv, qkv_norm, inv, logit_scale)
+    rows = dqkv.shape[0]
+    ls = _f32c(logit_scale, "logit_scale")
+    if dqkv.dtype != qkv_norm.dtype or qkv_norm.shape[0] != rows or min(dqkv.shape[1], qkv_norm.shape[1]) < 3 * H * d:
+        raise ValueError("swin_qk_norm_bwd: dqkv and qkv_norm must be packed [rows, 3*H*d] rows of one dtype")
+    if _f32c(inv, "inv").numel() != rows * 2 * H or ls.numel() != H:
+        raise ValueError("swin_qk_norm_bwd: inv must be [rows, 2, H] and logit_scale hold H values")
+    nws = lib().mmfd_swin_qk_norm_bwd_workspace_bytes(rows, H)
+    ws = torch.empty(max(nws // 4, 1), device=dqkv.device, dtype=torch.float32)
+    dls = torch.empty(H, device=dqkv.device, dtype=torch.float32)
+    _check(lib().mmfd_swin_qk_norm_bwd(dtype_code(dqkv.dtype), rows, H, d, _ptr(dqkv), _ld(dqkv), _ptr(qkv_norm),
+                                       _ld(qkv_norm), _ptr(inv), _ptr(ls), float(max_log), _ptr(dls), _ptr(ws), nws,
+                                       _stream()), "mmfd_swin_qk_norm_bwd")
+    return dqkv, dls
+
+
+def swin_bias_bwd(d_bias, table, rpi, L):
+    """adjoint of swin_bias: d_bias fp32 [nW, H, L, L] -> d_table fp32 [T, H] (the mask takes no gradient)"""
+    _require_cuda(d_bias, table, rpi)
+    T, H = table.shape
+    if _f32c(d_bias, "d_bias").dim() != 4 or tuple(d_bias.shape[1:]) != (H, L, L):
+        raise ValueError("swin_bias_bwd: d_bias must be [nW, H, L, L]")
+    if rpi.dtype != torch.int32 or rpi.numel() != L * L or not rpi.is_contiguous():
+        raise ValueError("swin_bias_bwd: rpi must be contiguous int32 [L*L]")
+    out = torch.empty((T, H), device=table.device, dtype=torch.float32)
+    _check(lib().mmfd_swin_bias_bwd(d_bias.shape[0], H, L, T, _ptr(d_bias), _ptr(_f32c(table, "table")), _ptr(rpi),
+                                    _ptr(out), _stream()), "mmfd_swin_bias_bwd")
+    return out
+
+
+def swin_cpb_bwd(d_table, coords, w1, b1, w2):
+    """adjoint of swin_cpb: (d_w1 [512, 2], d_b1 [512], d_w2 [H, 512]) fp32 from d_table [T, H]"""
+    _require_cuda(d_table, coords, w1, b1, w2)
+    T, H = d_table.shape
+    if tuple(w1.shape) != (512, 2) or tuple(w2.shape) != (H, 512) or b1.numel() != 512 or tuple(coords.shape) != (T, 2):
+        raise ValueError("swin_cpb_bwd: coords [T, 2], w1 [512, 2], b1 [512], w2 [H, 512], d_table [T, H]")
+    for t, n in ((d_table, "d_table"), (coords, "coords"), (w1, "w1"), (b1, "b1"), (w2, "w2")):
+        _f32c(t, n)
+    dw1, db1, dw2 = (torch.empty(t.shape, device=d_table.device, dtype=torch.float32) for t in (w1, b1, w2))
+    _check(lib().mmfd_swin_cpb_bwd(T, H, _ptr(coords), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(d_table), _ptr(dw1),
+                                   _ptr(db1), _ptr(dw2), _stream()), "mmfd_swin_cpb_bwd")
+    return dw1, db1, dw2

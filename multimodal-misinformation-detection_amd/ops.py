@@ -1,7 +1,7 @@
 """Fake (meta) kernels of the torch.ops.mmfd custom ops registered by libmmfd_torch.so
 (csrc/torch_ops.cpp), so the ops trace under FakeTensorMode / torch.compile / the meta device:
 the out-variant ops (the C ABI never allocates) only mutate their declared out arguments and
-return nothing (attn_bwd's optional `d_rel_bias` is one more declared out argument); `mmfd::linear`
+return nothing (attn_bwd's optional `d_rel_bias` and `delta` are two more declared out arguments); `mmfd::linear`
 returns its [..., N] output. Imported by mmfd.kernels.load()."""
 from __future__ import annotations
 

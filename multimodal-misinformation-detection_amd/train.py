@@ -433,10 +433,15 @@ def parse_args(argv=None):
     ap.add_argument("--image_input_dim", type=int, default=1024)
     # mmfd
     ap.add_argument("--image_encoder", type=str, default="microsoft/swinv2-base-patch4-window8-256",
-                    help="microsoft/swinv2-base-patch4-window8-256 (frozen) or google/vit-base-patch16-224")
+                    help="microsoft/swinv2-base-patch4-window8-256 (frozen unless --train_image_encoder) or "
+                         "google/vit-base-patch16-224")
     ap.add_argument("--train_text_encoder", action="store_true",
                     help="fine-tune microsoft/deberta-v3-xsmall (no dropout) instead of freezing it; --freeze_text "
                          "wins; no effect on bert-base-uncased, which trains unless --freeze_text")
+    ap.add_argument("--train_image_encoder", action="store_true",
+                    help="fine-tune microsoft/swinv2-base-patch4-window8-256 (no stochastic depth) instead of freezing "
+                         "it; --freeze_image wins; no effect on google/vit-base-patch16-224, which trains unless "
+                         "--freeze_image")
     ap.add_argument("--precision", choices=["fp32", "bf16"], default="fp32")
     ap.add_argument("--synthetic", type=int, default=0,
                     help="train on N synthetic Factify-shaped pairs instead of --train_data")
@@ -451,10 +456,11 @@ IMAGE_ENCODERS = ("microsoft/swinv2-base-patch4-window8-256", "google/vit-base-p
 
 
 def build_encoders(args, device):
-    """the encoders of train.py:329-340 (random init: no hub download here). Swinv2 is an inference
-    encoder in mmfd and therefore always frozen, as in the reference; so is DeBERTa-v3 by default,
-    and with --train_text_encoder (and no --freeze_text) it is built trainable
-    (DebertaV2Config(trainable=True), dropout 0) and fine-tuned; bert-base / ViT-B/16 train unless
+    """the encoders of train.py:329-340 (random init: no hub download here). DeBERTa-v3 and Swinv2
+    are inference encoders by default and then frozen; with --train_text_encoder (and no
+    --freeze_text) DeBERTa-v3 is built trainable (DebertaV2Config(trainable=True), dropout 0) and
+    fine-tuned, with --train_image_encoder (and no --freeze_image) Swinv2 is
+    (Swinv2Config(trainable=True), no stochastic depth); bert-base / ViT-B/16 train unless
     --freeze_text / --freeze_image."""
     if args.text_encoder == "microsoft/deberta-v3-xsmall":
         from .deberta import DebertaV2Config, DebertaV2Model
@@ -466,7 +472,8 @@ def build_encoders(args, device):
         raise ValueError(f"--text_encoder must be one of {TEXT_ENCODERS}")
     if args.image_encoder == "microsoft/swinv2-base-patch4-window8-256":
         from .swinv2 import Swinv2Config, Swinv2Model
-        image, image_frozen = Swinv2Model(Swinv2Config()), True
+        trainable = bool(getattr(args, "train_image_encoder", False)) and not args.freeze_image
+        image, image_frozen = Swinv2Model(Swinv2Config(trainable=trainable)), not trainable
     elif args.image_encoder == "google/vit-base-patch16-224":
         image, image_frozen = ViTModel(ViTConfig()), args.freeze_image
     else:
