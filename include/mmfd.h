@@ -488,6 +488,44 @@ int mmfd_swin_cpb_bwd(int64_t T, int64_t H, const float* coords, const float* w1
                       mmfd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------- */
+/* Greedy autoregressive decoding (the reference's captioning stage: src/preprocess/caption.py  */
+/* :22-31 and src/demo/app.py run BlipForConditionalGeneration.generate(**inputs); csrc/        */
+/* decode.hip, mmfd/blip.py). One token per row and step; every length is a host argument.      */
+/* ------------------------------------------------------------------------------------------- */
+/* Single-token attention: o[b][h*D + :] = softmax_k(scale * q[b][h] . k[b][key][h]) v[b][key][h] over
+   keys 0 .. Lk-1. q at base + b*q_sb + h*D, k / v at base + b*s_b + key*s_t + h*D (elements: views into a
+   packed K|V cache work), o at base + b*o_sb + h*D. Rows at and past Lk are never read. fp32 or bf16
+   storage, fp32 accumulation; D is 32 or 64; q, k, v pointers and strides multiples of 16 bytes. The key
+   range is split over mmfd_attn_decode_splits(B, H, Lk) waves per (b, h) (one 64-key step each until about
+   1024 waves run; at most 32) and combined by a second kernel: with more than one split `workspace` must
+   hold mmfd_attn_decode_workspace_bytes (fp32 {max, sum, acc[D]} per split), else it may be NULL. */
+int mmfd_attn_decode_splits(int64_t B, int64_t H, int64_t Lk);
+int64_t mmfd_attn_decode_workspace_bytes(int64_t B, int64_t H, int64_t D, int64_t Lk);
+int mmfd_attn_decode(int dtype, int64_t B, int64_t H, int64_t D, int64_t Lk, float scale, const void* q,
+                     int64_t q_sb, const void* k, int64_t k_sb, int64_t k_st, const void* v, int64_t v_sb,
+                     int64_t v_st, void* o, int64_t o_sb, void* workspace, int64_t workspace_bytes,
+                     mmfd_stream_t stream);
+/* LM head with the argmax fused: out_idx[b] = argmax_v (x[b] . W[v] + bias[v]) for x [B][ldx] and W [V][ldw]
+   in dtype (the tied embedding table as it lies; rows 16-byte aligned), bias fp32 [V] or NULL, B <= 32,
+   K a multiple of 16 bytes and <= 256 * 16 bytes. fp32 operands are multiplied with fp32 FMAs (never on
+   split bf16 planes), bf16 operands accumulate in fp32. Each workgroup streams one slab of
+   mmfd_lm_head_argmax_slab consecutive rows of W once for all B rows and keeps a (max, index) per row;
+   a second kernel reduces the per-workgroup partials. Ties go to the lowest index, a NaN is never chosen
+   over a number. logits (fp32 [B][ldl], optional) receives every logit. workspace >=
+   mmfd_lm_head_argmax_workspace_bytes. */
+int64_t mmfd_lm_head_argmax_workspace_bytes(int dtype, int64_t B, int64_t V, int64_t K);
+int64_t mmfd_lm_head_argmax_slab(int dtype, int64_t B, int64_t V, int64_t K);
+int mmfd_lm_head_argmax(int dtype, int64_t B, int64_t V, int64_t K, const void* x, int64_t ldx, const void* W,
+                        int64_t ldw, const float* bias, int64_t* out_idx, float* logits, int64_t ldl,
+                        void* workspace, int64_t workspace_bytes, mmfd_stream_t stream);
+/* The greedy rule of one step, per row b: tok = forced[b*forced_ld] when forced != NULL (a prompt or
+   teacher forcing), else pad when finished[b] was set before this step, else argmax[b];
+   next[b*next_ld] = tok; finished[b] |= (tok == eos). finished: int32 [B]. */
+int mmfd_greedy_select(int64_t B, const int64_t* argmax, const int64_t* forced, int64_t forced_ld,
+                       int32_t* finished, int64_t eos, int64_t pad, int64_t* next, int64_t next_ld,
+                       mmfd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------- */
 /* AdamW (torch.optim.AdamW defaults as used at train.py:356/188), multi-tensor, one launch.    */
 /* table: device array of n_tensors records {param f32*, grad f32*, exp_avg f32*, exp_avg_sq     */
 /* f32*, param_bf16 bf16* (optional shadow copy, may be NULL), step f32*, numel};             */

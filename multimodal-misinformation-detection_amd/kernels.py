@@ -29,6 +29,7 @@ TORCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libmmfd_torch.so")
 F32, BF16, F16 = 0, 1, 2
 ABI_VERSION = 3  # include/mmfd.h MMFD_ABI_VERSION: the layout of the argument structs below
 COS_PAIR, COS_NORMALIZED, COS_ROUND_F16 = 0, 1, 4
+MMFD_ERR_INVALID = 1000  # include/mmfd.h: what a failed query function (-1) is reported as
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_GELU_BWD, ACT_RELU_BWD, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3, 4, 5, 6
 # GELU whose aux keeps gelu'(pre-activation), and its backward (out *= aux): the training FFNs
 ACT_GELU_D, ACT_MUL_AUX = 7, 8
@@ -205,6 +206,14 @@ SIGNATURES = {
     "mmfd_attn_bwd_bias_sum": (_I, [ctypes.POINTER(AttnArgs), _VP, _VP]),
     "mmfd_swin_bias_bwd": (_I, [_I64, _I64, _I64, _I64, _VP, _VP, _VP, _VP, _VP]),
     "mmfd_swin_cpb_bwd": (_I, [_I64, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mmfd_attn_decode_splits": (_I, [_I64, _I64, _I64]),
+    "mmfd_attn_decode_workspace_bytes": (_I64, [_I64, _I64, _I64, _I64]),
+    "mmfd_attn_decode": (_I, [_I, _I64, _I64, _I64, _I64, _F, _VP, _I64, _VP, _I64, _I64, _VP, _I64, _I64, _VP, _I64,
+                              _VP, _I64, _VP]),
+    "mmfd_lm_head_argmax_workspace_bytes": (_I64, [_I, _I64, _I64, _I64]),
+    "mmfd_lm_head_argmax_slab": (_I64, [_I, _I64, _I64, _I64]),
+    "mmfd_lm_head_argmax": (_I, [_I, _I64, _I64, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _VP, _I64, _VP, _I64, _VP]),
+    "mmfd_greedy_select": (_I, [_I64, _VP, _VP, _I64, _VP, _I64, _I64, _VP, _I64, _VP]),
 }
 
 _lib = None
@@ -1430,3 +1439,96 @@ def swin_cpb_bwd(d_table, coords, w1, b1, w2):
     _check(lib().mmfd_swin_cpb_bwd(T, H, _ptr(coords), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(d_table), _ptr(dw1),
                                    _ptr(db1), _ptr(dw2), _stream()), "mmfd_swin_cpb_bwd")
     return dw1, db1, dw2
+
+
+# -------------------------------------------------------------------------------------------------
+# greedy decoding (csrc/decode.hip)
+# -------------------------------------------------------------------------------------------------
+def attn_decode_splits(B, H, Lk):
+    """how many waves share the key range of one (b, h) in attn_decode (the library's own rule)"""
+    s = lib().mmfd_attn_decode_splits(int(B), int(H), int(Lk))
+    _check(0 if s > 0 else MMFD_ERR_INVALID, "mmfd_attn_decode_splits")
+    return s
+
+
+def attn_decode(q, k, v, H, Lk, *, scale=None, out=None, workspace=None):
+    """single-token attention: q [B, H*D], k / v [B, Lmax, H*D] (views into a packed cache are fine), keys
+    0 .. Lk-1 only (rows past Lk are never read); returns o [B, H*D]. `workspace`: a uint8 tensor of
+    mmfd_attn_decode_workspace_bytes (allocated here when the key range is split and none is given)."""
+    _require_cuda(q, k, v, out, workspace)
+    if q.dim() != 2 or k.dim() != 3 or v.dim() != 3 or q.stride(1) != 1 or k.stride(2) != 1 or v.stride(2) != 1:
+        raise ValueError("attn_decode: q [B, H*D] and k / v [B, Lmax, H*D] views with a contiguous last dim")
+    if k.dtype != q.dtype or v.dtype != q.dtype:
+        raise TypeError("attn_decode: q, k, v must share a dtype")
+    B, HD = q.shape
+    D = HD // H
+    if Lk > k.shape[1] or Lk > v.shape[1]:
+        raise ValueError(f"attn_decode: Lk = {Lk} exceeds the cache rows ({k.shape[1]})")
+    if out is None:
+        out = torch.empty((B, HD), device=q.device, dtype=q.dtype)
+    elif out.dtype != q.dtype or tuple(out.shape) != (B, HD) or out.stride(1) != 1:
+        raise ValueError("attn_decode: out must be a [B, H*D] view of q's dtype with a contiguous last dim")
+    need = lib().mmfd_attn_decode_workspace_bytes(B, H, D, int(Lk)) if B and Lk > 0 and D > 0 else 0
+    if need > 0 and (workspace is None or workspace.numel() * workspace.element_size() < need):
+        workspace = torch.empty(need, device=q.device, dtype=torch.uint8)
+    _check(lib().mmfd_attn_decode(dtype_code(q.dtype), B, H, D, int(Lk), float(scale if scale is not None else D ** -0.5),
+                                  _ptr(q), q.stride(0), _ptr(k), k.stride(0), k.stride(1), _ptr(v), v.stride(0),
+                                  v.stride(1), _ptr(out), out.stride(0), _ptr(workspace),
+                                  workspace.numel() * workspace.element_size() if workspace is not None else 0,
+                                  _stream()), "mmfd_attn_decode")
+    return out
+
+
+def lm_head_slab(dtype, B, V, K):
+    """vocabulary rows per workgroup of lm_head_argmax for these shapes"""
+    s = lib().mmfd_lm_head_argmax_slab(dtype_code(dtype), int(B), int(V), int(K))
+    _check(0 if s > 0 else MMFD_ERR_INVALID, "mmfd_lm_head_argmax_slab")
+    return int(s)
+
+
+def lm_head_argmax(x, W, bias=None, *, out=None, logits=None, workspace=None):
+    """argmax_v (x @ W^T + bias) per row without writing the logits: x [B <= 32, K], W [V, K] (row-major
+    views, one dtype), bias fp32 [V]. Returns int64 [B]; `logits` (fp32 [B, V] view) also receives them."""
+    _require_cuda(x, W, bias, out, logits, workspace)
+    if x.dtype != W.dtype:
+        raise TypeError(f"lm_head_argmax operands must share a dtype ({x.dtype} vs {W.dtype})")
+    B, Kd = x.shape
+    V = W.shape[0]
+    if W.shape[1] != Kd:
+        raise ValueError(f"lm_head_argmax inner dims differ: {Kd} vs {W.shape[1]}")
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != V or not bias.is_contiguous()):
+        raise ValueError("bias must be a contiguous fp32 vector of length V")
+    if logits is not None and (logits.dtype != torch.float32 or tuple(logits.shape) != (B, V)):
+        raise ValueError("logits must be an fp32 [B, V] view")
+    if out is None:
+        out = torch.empty(B, device=x.device, dtype=torch.int64)
+    elif out.dtype != torch.int64 or out.numel() != B or not out.is_contiguous():
+        raise ValueError("out must be a contiguous int64 vector of length B")
+    code = dtype_code(x.dtype)
+    need = lib().mmfd_lm_head_argmax_workspace_bytes(code, B, V, Kd)
+    _check(0 if need > 0 else MMFD_ERR_INVALID, "mmfd_lm_head_argmax")
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(need, device=x.device, dtype=torch.uint8)
+    _check(lib().mmfd_lm_head_argmax(code, B, V, Kd, _ptr(x), _ld(x), _ptr(W), _ld(W), _ptr(bias), _ptr(out),
+                                     _ptr(logits), _ld(logits) if logits is not None else 0, _ptr(workspace),
+                                     workspace.numel() * workspace.element_size(), _stream()), "mmfd_lm_head_argmax")
+    return out
+
+
+def greedy_select(argmax, finished, eos, pad, next_tokens, forced=None):
+    """one greedy step per row: next_tokens[b] = forced[b] if given, else pad if finished[b], else argmax[b];
+    finished[b] |= (token == eos). argmax / forced / next_tokens: int64 [B] views (any stride), finished
+    int32 [B] contiguous, updated in place."""
+    _require_cuda(argmax, finished, next_tokens, forced)
+    B = finished.numel()
+    for t in (argmax, forced, next_tokens):
+        if t is not None and (t.dtype != torch.int64 or t.dim() != 1 or t.numel() != B):
+            raise ValueError("greedy_select: argmax / forced / next_tokens must be int64 [B] views")
+    if finished.dtype != torch.int32 or not finished.is_contiguous():
+        raise ValueError("greedy_select: finished must be a contiguous int32 [B] tensor")
+    if argmax is not None and argmax.stride(0) != 1:
+        raise ValueError("greedy_select: argmax must be contiguous")
+    _check(lib().mmfd_greedy_select(B, _ptr(argmax), _ptr(forced), forced.stride(0) if forced is not None else 0,
+                                    _ptr(finished), int(eos), int(pad), _ptr(next_tokens), next_tokens.stride(0),
+                                    _stream()), "mmfd_greedy_select")
+    return next_tokens
