@@ -505,6 +505,13 @@ int mmfd_attn_decode(int dtype, int64_t B, int64_t H, int64_t D, int64_t Lk, flo
                      int64_t q_sb, const void* k, int64_t k_sb, int64_t k_st, const void* v, int64_t v_sb,
                      int64_t v_st, void* o, int64_t o_sb, void* workspace, int64_t workspace_bytes,
                      mmfd_stream_t stream);
+/* The same with `group` query rows per row of k / v: query row b attends k / v row b / group (beam search: the
+   beams of an image share its cross-attention keys). B query rows, B % group == 0, k / v hold B / group rows;
+   splits and workspace as mmfd_attn_decode for B rows. */
+int mmfd_attn_decode_grouped(int dtype, int64_t B, int64_t group, int64_t H, int64_t D, int64_t Lk, float scale,
+                             const void* q, int64_t q_sb, const void* k, int64_t k_sb, int64_t k_st, const void* v,
+                             int64_t v_sb, int64_t v_st, void* o, int64_t o_sb, void* workspace,
+                             int64_t workspace_bytes, mmfd_stream_t stream);
 /* LM head with the argmax fused: out_idx[b] = argmax_v (x[b] . W[v] + bias[v]) for x [B][ldx] and W [V][ldw]
    in dtype (the tied embedding table as it lies; rows 16-byte aligned), bias fp32 [V] or NULL, B <= 32,
    K a multiple of 16 bytes and <= 256 * 16 bytes. fp32 operands are multiplied with fp32 FMAs (never on
@@ -524,6 +531,44 @@ int mmfd_lm_head_argmax(int dtype, int64_t B, int64_t V, int64_t K, const void* 
 int mmfd_greedy_select(int64_t B, const int64_t* argmax, const int64_t* forced, int64_t forced_ld,
                        int32_t* finished, int64_t eos, int64_t pad, int64_t* next, int64_t next_ld,
                        mmfd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------- */
+/* Beam search for the same decoder (csrc/beam.hip): transformers' GenerationMixin._beam_search  */
+/* with one eos token, no logits processors and no sampling. B images of nb <= 8 beams each; row */
+/* b*nb + j is beam j of image b. Every length and the step number are host arguments.           */
+/* ------------------------------------------------------------------------------------------- */
+/* Candidate selection: for logits fp32 [B*nb][ldl] and running fp32 [B*nb], per image the 2 nb best
+   candidates (out_score, out_beam, out_token: [B][2 nb], best first) of its nb*V, score =
+   (logit - logsumexp(row)) + running[row] in fp32. Order: the larger score, equal scores by the lower flat
+   index beam*V + token, a NaN after every number (NaNs by index; a NaN logit is also left out of its row's
+   logsumexp), so the indices are always valid and distinct. 2 nb <= V <= 2^20. Each row is spread over
+   workgroups of mmfd_beam_select_slab(V) entries; workspace: 8-byte aligned,
+   >= mmfd_beam_select_workspace_bytes. */
+int64_t mmfd_beam_select_slab(int64_t V);
+int64_t mmfd_beam_select_workspace_bytes(int64_t B, int64_t nb, int64_t V);
+int mmfd_beam_select(int64_t B, int64_t nb, int64_t V, const float* logits, int64_t ldl, const float* running,
+                     float* out_score, int32_t* out_beam, int32_t* out_token, void* workspace,
+                     int64_t workspace_bytes, mmfd_stream_t stream);
+/* One beam step on device state, from the candidates above (steps d - g of _beam_search). The step embeds
+   position t and chooses the token of position t + 1 < T; gen_len = tokens generated once it is chosen;
+   last != 0: position t + 1 is the last one (every candidate stops); len_div = gen_len ** length_penalty.
+     run_score, fin_score fp32 [B][nb]; fin_flag, fin_len int32 [B][nb] (is_sent_finished and the generated
+     length of each stored hypothesis); run_seq, fin_seq int32 [B][nb][T]; flags int32 [B][4] = {early-stop
+     heuristic still unsatisfied (read and written), every stored hypothesis finished, every candidate
+     stopped, unused}; parent int32 [B*nb]: the row whose cache the new row continues;
+     next[(b*nb + j)*next_ld]: the token of new beam j.
+   Selections use the candidates' order; the fp32 operations are torch's, in its order. */
+int mmfd_beam_update(int64_t B, int64_t nb, int64_t T, int64_t t, int64_t gen_len, int last, int early_stopping,
+                     int64_t eos, float len_div, const float* cand_score, const int32_t* cand_beam,
+                     const int32_t* cand_token, float* run_score, float* fin_score, int32_t* fin_flag,
+                     int32_t* fin_len, int32_t* run_seq, int32_t* fin_seq, int32_t* flags, int32_t* parent,
+                     int64_t* next, int64_t next_ld, mmfd_stream_t stream);
+/* Cache reorder, all layers in one launch: for every layer l and row r < rows the first `bytes` bytes of
+   dst[l] + r*row_stride_bytes become those of src[l] + from*row_stride_bytes, from = parent[r] for
+   r < beam_rows (a parent outside [0, beam_rows) is not followed), else r. src / dst: device arrays of
+   `layers` 16-byte aligned device pointers, src[l] != dst[l]; bytes and the stride multiples of 16. */
+int mmfd_beam_reorder(int64_t layers, int64_t rows, int64_t beam_rows, int64_t row_stride_bytes, int64_t bytes,
+                      const void* const* src, void* const* dst, const int32_t* parent, mmfd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------- */
 /* AdamW (torch.optim.AdamW defaults as used at train.py:356/188), multi-tensor, one launch.    */

@@ -4,7 +4,7 @@ large").generate(**inputs)` over every claim and evidence image). Inference only
 
 `BlipForConditionalGeneration` keeps transformers' parameter names, so its `state_dict` loads with
 `strict=True`; `generate` follows transformers' greedy default (20 new tokens, decoding from [bos], stop
-at sep_token_id, pad afterwards).
+at sep_token_id, pad afterwards) or, with num_beams > 1, its beam search (csrc/beam.hip; the last item below).
 
 What runs where:
   * vision tower (pre-LN ViT, packed qkv): patchify + GEMM, class token + positions, then per layer
@@ -19,6 +19,12 @@ What runs where:
     the token, kernels.greedy_select applies the stop / pad / forced-token rule and writes the token
     where the next step's embedding kernel reads it. No token visits the host between steps, so the
     whole unrolled loop (vision tower included) is one captured HIP graph per (batch, steps, precision).
+  * beam search: B images x nb beams are B * nb decoder rows that share the image's cross-attention K|V. A step
+    writes its fp32 logits, kernels.beam_select leaves the 2 nb best (score, beam, token) per image,
+    kernels.beam_update does transformers' bookkeeping on device state (running and finished hypotheses, the
+    early-stop heuristic, the next token and the parent row of every beam) and kernels.beam_reorder gathers the
+    self-attention caches by parent into a second set of buffers: still no host decision between steps and one
+    captured graph per (batch, steps, precision, num_beams, length_penalty, early_stopping).
 """
 from __future__ import annotations
 
@@ -306,9 +312,11 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
             out.append(K.gemm(Bk.as2d(emb), W, bias=b).view(B, Li, -1))
         return out
 
-    def _step(self, sc, st, cross, t, forced, logits=None, select=True):
-        """decoder step t: embeds st['seq'][t] at position t, appends its K|V to the self cache, and
-        (select) writes the next token to st['seq'][t + 1]"""
+    def _hidden(self, sc, st, cross, t, self_kv, nb=1):
+        """the decoder body of step t: embeds st['seq'][t] at position t, appends its K|V to row t of the caches
+        `self_kv`, and returns the LM head's input [Bp, E]. nb > 1: rows b*nb .. b*nb + nb - 1 are the beams of
+        image b and attend the one cross-attention K|V of that image (attn_decode's group argument: no copy of the
+        image keys per beam)"""
         tc = self.config.text
         E, H, eps, B, Bp = tc.hidden_size, tc.num_attention_heads, tc.layer_norm_eps, st["B"], st["Bp"]
         P = sc.P
@@ -319,7 +327,7 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
             p = f"{T}encoder.layer.{i}"
             q, _ = Bk.linear(sc, x, p + ".attention.self.query")
             Wkv, bkv = self._packed(sc, [p + ".attention.self.key", p + ".attention.self.value"])
-            kv = st["self_kv"][i]
+            kv = self_kv[i]
             K.gemm(x, Wkv, bias=bkv, out=kv[:, t, :])  # row t of the cache is the GEMM's output
             o = K.attn_decode(q, kv[..., :E], kv[..., E:], H, t + 1, workspace=st["attn_ws"])
             s1, _ = Bk.linear(sc, o, p + ".attention.output.dense", residual=x)
@@ -327,7 +335,11 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
             cq, _ = Bk.linear(sc, h, p + ".crossattention.self.query")
             ckv = cross[i]  # every image key takes part (transformers passes an all-ones mask)
             co = st["cross_o"]
-            K.attn_decode(cq[:B], ckv[..., :E], ckv[..., E:], H, ckv.shape[1], out=co[:B], workspace=st["attn_ws"])
+            if nb == 1:
+                K.attn_decode(cq[:B], ckv[..., :E], ckv[..., E:], H, ckv.shape[1], out=co[:B], workspace=st["attn_ws"])
+            else:
+                K.attn_decode(cq[:B * nb], ckv[..., :E], ckv[..., E:], H, ckv.shape[1], out=co[:B * nb],
+                              workspace=st["attn_ws"], group=nb)
             s2, _ = Bk.linear(sc, co, p + ".crossattention.output.dense", residual=h)
             h2, _, _ = Bk.layernorm(sc, s2, p + ".crossattention.output.LayerNorm", eps)
             s3, _ = Bk.ffn_fwd(sc, h2, p + ".intermediate.dense", p + ".output.dense", residual=h2, keep=False,
@@ -335,6 +347,14 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
             x, _, _ = Bk.layernorm(sc, s3, p + ".output.LayerNorm", eps)
         g, _ = Bk.linear(sc, x, HEAD + "transform.dense", act=K.ACT_GELU)
         g, _, _ = Bk.layernorm(sc, g, HEAD + "transform.LayerNorm", eps)
+        return g
+
+    def _step(self, sc, st, cross, t, forced, logits=None, select=True):
+        """decoder step t: embeds st['seq'][t] at position t, appends its K|V to the self cache, and
+        (select) writes the next token to st['seq'][t + 1]"""
+        tc = self.config.text
+        B, P = st["B"], sc.P
+        g = self._hidden(sc, st, cross, t, st["self_kv"])
         K.lm_head_argmax(g[:B], sc.w(WORD), P[HEAD + "bias"], out=st["argmax"], logits=logits, workspace=st["lm_ws"])
         if select:
             K.greedy_select(st["argmax"], st["finished"], tc.sep_token_id, tc.pad_token_id, st["seq"][t + 1, :B],
@@ -369,18 +389,35 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
         return [int(i) for i in ids]
 
     @torch.no_grad()
-    def generate(self, pixel_values, input_ids=None, max_new_tokens=20, use_graph=True):
-        """Greedy captions: int64 [B, P + n] ids (the prompt, bos first, then n <= max_new_tokens generated
+    def generate(self, pixel_values, input_ids=None, max_new_tokens=20, use_graph=True, num_beams=1,
+                 length_penalty=1.0, early_stopping=False):
+        """Captions, greedy (num_beams=1) or by beam search (below). Greedy: int64 [B, P + n] ids (the prompt, bos first, then n <= max_new_tokens generated
         tokens: a row that produced sep_token_id is padded with pad_token_id, and n is where the last row
         stopped) — the array transformers' `generate(pixel_values, input_ids)` returns by default.
         `input_ids`: an optional prompt shared by all rows, fed one token per step in place of the argmax.
         use_graph: replay one captured HIP graph of all steps and trim on the host; else run eagerly and
-        stop once every row has finished."""
+        stop once every row has finished.
+        num_beams in 2 .. 8 (num_beams * batch <= 32, the LM head's rows): transformers' beam search with
+        `length_penalty` and `early_stopping` (False or True), no sampling, one returned sequence per image — the
+        array `generate(pixel_values, input_ids, num_beams=..., length_penalty=..., early_stopping=...,
+        max_new_tokens=...)` returns there, unused positions filled as transformers fills them
+        (`pad_token_id or sep_token_id`). `self.sequences_scores` then holds the fp32 scores [B] of the returned
+        hypotheses. Among equal scores the lower beam, then the lower token wins (torch.topk leaves that open)."""
         tc = self.config.text
+        B = int(pixel_values.shape[0])
+        if early_stopping not in (False, True):
+            raise ValueError(f"early_stopping must be False or True, got {early_stopping!r} ('never' is not implemented)")
+        if int(num_beams) != num_beams or not 1 <= num_beams <= 8:
+            raise ValueError(f"num_beams must lie in [1, 8], got {num_beams}")
+        if num_beams > 1 and (num_beams > tc.vocab_size // 2 or B * num_beams > 32):
+            raise ValueError(f"beam search needs num_beams <= vocab_size / 2 and batch * num_beams <= 32 (the LM head "
+                             f"kernel's rows), got batch {B}, num_beams {num_beams}, vocabulary {tc.vocab_size}")
         sc, dev = self._ctx()
         px = pixel_values.to(dev).float().contiguous()
-        B = px.shape[0]
         prompt = self._prompt(input_ids)
+        if num_beams > 1:
+            return self._generate_beams(sc, dev, px, prompt, int(max_new_tokens), bool(use_graph), int(num_beams),
+                                        float(length_penalty), bool(early_stopping))
         n_forced = len(prompt) - 1
         steps = n_forced + int(max_new_tokens)
         if steps < 1 or steps + 1 > tc.max_position_embeddings:
@@ -411,18 +448,142 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
                 break
         return st["seq"][:n + 1, :B].t().contiguous().cpu()
 
-    def _capture(self, st, n_forced, dev):
+    def _capture(self, st, n_forced, dev, run=None):
+        run = run or self._run
         st["graph"] = None
         st["sig"], st["n_forced"] = self._signature(), n_forced
         s = torch.cuda.Stream(device=dev)
         s.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(s):
-            self._run(st, n_forced)  # warm up: weight shadows, packed biases, kernel attributes
+            run(st, n_forced)  # warm up: weight shadows, packed biases, kernel attributes
         torch.cuda.current_stream(dev).wait_stream(s)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self._run(st, n_forced)
+            run(st, n_forced)
         st["graph"] = g
+
+    # ---- beam search ---------------------------------------------------------------------------------
+    def _beam_state(self, B, steps, dev, nb, lp, early):
+        """the device buffers of one (batch, steps, precision, beam parameters): what _state holds for B * nb rows,
+        a second set of self-attention caches (the reorder gathers from one into the other), the fp32 logits of
+        one step and the search state of csrc/beam.hip"""
+        key = (B, steps, self.compute_dtype, str(dev), nb, lp, early)
+        st = self._states.get(key)
+        if st is not None:
+            return st
+        vc, tc = self.config.vision, self.config.text
+        dt, E, H, L = self.compute_dtype, tc.hidden_size, tc.num_attention_heads, tc.num_hidden_layers
+        Li = (vc.image_size // vc.patch_size) ** 2 + 1
+        R, T = B * nb, steps + 1
+        Bp = max(R, 16)
+        i32 = dict(dtype=torch.int32, device=dev)
+        kv = [[torch.zeros(Bp, steps, 2 * E, device=dev, dtype=dt) for _ in range(L)] for _ in range(2)]
+        st = dict(
+            B=B, Bp=Bp, R=R, nb=nb, lp=lp, early=early, steps=steps, Li=Li,
+            px=torch.zeros(B, vc.num_channels, vc.image_size, vc.image_size, device=dev),
+            seq=torch.zeros(T, Bp, dtype=torch.int64, device=dev),
+            pos=torch.arange(T, dtype=torch.int64, device=dev)[:, None].expand(T, Bp).contiguous(),
+            argmax=torch.zeros(R, dtype=torch.int64, device=dev),
+            kv=kv, kv_table=[K.ptr_table(kv[0]), K.ptr_table(kv[1])],
+            cross_o=torch.zeros(Bp, E, device=dev, dtype=dt),
+            logits=torch.zeros(R, tc.vocab_size, device=dev),
+            cand=(torch.zeros(B, 2 * nb, device=dev), torch.zeros(B, 2 * nb, **i32), torch.zeros(B, 2 * nb, **i32)),
+            beam=dict(run_score=torch.zeros(B, nb, device=dev), fin_score=torch.zeros(B, nb, device=dev),
+                      fin_flag=torch.zeros(B, nb, **i32), fin_len=torch.zeros(B, nb, **i32),
+                      run_seq=torch.zeros(B, nb, T, **i32), fin_seq=torch.zeros(B, nb, T, **i32),
+                      flags=torch.zeros(B, 4, **i32), parent=torch.zeros(R, **i32)),
+            graph=None, sig=None, n_forced=-1)
+        need = max(K.lib().mmfd_attn_decode_workspace_bytes(B, H, E // H, Li),
+                   K.lib().mmfd_attn_decode_workspace_bytes(R, H, E // H, Li),
+                   K.lib().mmfd_attn_decode_workspace_bytes(Bp, H, E // H, steps), 16)
+        st["attn_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+        need = K.lib().mmfd_lm_head_argmax_workspace_bytes(K.dtype_code(dt), R, tc.vocab_size, E)
+        if need <= 0:
+            raise ValueError(f"mmfd BLIP: the LM head kernel takes at most 32 rows and widths up to 1024 (fp32) / 2048 "
+                             f"(bf16), got {R} rows, width {E}")
+        st["lm_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+        st["sel_ws"] = torch.empty(K.beam_select_workspace_bytes(B, nb, tc.vocab_size), dtype=torch.uint8, device=dev)
+        if len(self._states) >= 8:
+            self._states.clear()
+        self._states[key] = st
+        return st
+
+    def _beam_begin(self, st, prompt):
+        """the state before the first step (transformers' step 3): every beam holds the prompt, which the forced
+        steps embed token by token; running scores [0, -1e9, ...]; nothing finished"""
+        tc = self.config.text
+        bs, R = st["beam"], st["R"]
+        ids = torch.tensor(prompt, dtype=torch.int64, device=st["seq"].device)
+        st["seq"].zero_()
+        st["seq"][:len(prompt), :R] = ids[:, None]
+        bs["run_seq"].fill_(tc.pad_token_id or tc.sep_token_id)  # transformers: `pad_token_id or eos_token_id[0]`
+        bs["run_seq"][:, :, :len(prompt)] = ids.int()
+        bs["fin_seq"].copy_(bs["run_seq"])
+        bs["run_score"].fill_(-1.0e9)
+        bs["run_score"][:, 0] = 0.0
+        bs["fin_score"].fill_(-1.0e9)
+        bs["fin_flag"].zero_()
+        bs["fin_len"].zero_()
+        bs["flags"].zero_()
+        bs["flags"][:, 0] = 1
+        bs["parent"].copy_(torch.arange(R, dtype=torch.int32, device=bs["parent"].device))
+
+    def _beam_unfinished(self, st):
+        """transformers' loop condition, from one host read of the per-image flags"""
+        f = st["beam"]["flags"].cpu().bool()
+        return bool(f[:, 0].any()) and not (st["early"] and bool(f[:, 1].all())) and not bool(f[:, 2].all())
+
+    def _beam_run(self, st, n_forced, eager=False):
+        """vision tower, cross K|V and every step. A forced step only feeds the decoder: its next token is the
+        prompt's, already in st['seq']. A free step writes the fp32 logits, selects the 2 nb candidates of every
+        image, updates the search state (which writes the next tokens and the parent rows) and gathers the
+        caches by parent into the other set. eager: leave once transformers would (the remaining steps change
+        nothing: every update of an image that cannot improve is masked)."""
+        tc = self.config.text
+        sc, _ = self._ctx()
+        R, nb, steps = st["R"], st["nb"], st["steps"]
+        cross = self._cross_kv(sc, self._vision(sc, st["px"]))
+        cur = 0
+        for t in range(steps):
+            g = self._hidden(sc, st, cross, t, st["kv"][cur], nb)
+            if t < n_forced:
+                continue
+            K.lm_head_argmax(g[:R], sc.w(WORD), sc.P[HEAD + "bias"], out=st["argmax"], logits=st["logits"],
+                             workspace=st["lm_ws"])
+            K.beam_select(st["logits"], st["beam"]["run_score"].view(-1), nb, out=st["cand"], workspace=st["sel_ws"])
+            K.beam_update(st["cand"], st["beam"], t, n_forced, t + 1 == steps, tc.sep_token_id, st["lp"], st["early"],
+                          st["seq"][t + 1, :R])
+            if t + 1 < steps:
+                K.beam_reorder(st["kv"][cur], st["kv"][1 - cur], st["kv_table"][cur], st["kv_table"][1 - cur],
+                               st["beam"]["parent"], R, t + 1)
+                cur = 1 - cur
+            if eager and not self._beam_unfinished(st):
+                break
+
+    def _generate_beams(self, sc, dev, px, prompt, max_new_tokens, use_graph, nb, lp, early):
+        tc = self.config.text
+        B = px.shape[0]
+        n_forced = len(prompt) - 1
+        steps = n_forced + max_new_tokens
+        if max_new_tokens < 1 or steps + 1 > tc.max_position_embeddings:
+            raise ValueError(f"prompt ({len(prompt)}) + max_new_tokens ({max_new_tokens}) must lie in "
+                             f"[2, {tc.max_position_embeddings}]")
+        st = self._beam_state(B, steps, dev, nb, lp, early)
+        if tuple(px.shape) != tuple(st["px"].shape):
+            raise ValueError(f"pixel_values must be {tuple(st['px'].shape)}, got {tuple(px.shape)}")
+        st["px"].copy_(px)
+        self._beam_begin(st, prompt)
+        if use_graph:
+            if st["graph"] is None or st["sig"] != self._signature() or st["n_forced"] != n_forced:
+                self._capture(st, n_forced, dev, run=self._beam_run)
+                self._beam_begin(st, prompt)
+            st["graph"].replay()
+        else:
+            self._beam_run(st, n_forced, eager=True)
+        bs = st["beam"]
+        n = int(bs["fin_len"][:, 0].max())  # transformers counts the entries of the chosen hypotheses' beam trail
+        self.sequences_scores = bs["fin_score"][:, 0].clone()
+        return bs["fin_seq"][:, 0, :len(prompt) + n].long().cpu().contiguous()
 
     @torch.no_grad()
     def _forward_logits(self, pixel_values, forced_ids):

@@ -2,10 +2,11 @@
 (`inputs = processor(image, return_tensors="pt"); out = model.generate(**inputs);
 processor.decode(out[0], skip_special_tokens=True)`) and the same call in src/demo/app.py.
 
-`Captioner` takes already preprocessed pixel tensors ([B, 3, S, S], BLIP's mean / std normalisation
-applied): BLIP's processor resizes with PIL's bicubic filter, which preprocess.hip does not have yet
-(bilinear taps only), so raw-image input is a follow-up, as are the resumable CSV driver, beam search /
-sampling, and training."""
+`Captioner` takes what the reference's processor takes — a PIL image, or a list of PIL images / uint8 HWC
+arrays, resized and normalised on the device by mmfd.preprocess.ImagePreprocessor("blip") bit for bit as
+transformers' BlipImageProcessor does it — or already preprocessed pixel tensors ([B, 3, S, S]). Decoding is
+greedy or, with num_beams > 1, transformers' beam search (mmfd.blip, csrc/beam.hip). Still to follow: the
+resumable CSV driver, sampling, and training."""
 from __future__ import annotations
 
 import torch
@@ -14,23 +15,46 @@ from .blip import BlipForConditionalGeneration
 
 
 class Captioner:
-    """captions for batches of preprocessed images: `.generate_ids(pixel_values)` -> int64 [B, 1 + n] ids
-    (bos first), `.caption(pixel_values)` -> list of B strings through `tokenizer` (any object with
-    transformers' `batch_decode(ids, skip_special_tokens=True)` or `decode`; loaded by the caller from a
-    local directory — nothing is fetched here)."""
+    """captions for batches of images: `.generate_ids(images)` -> int64 [B, 1 + n] ids (bos first),
+    `.caption(images)` -> list of B strings through `tokenizer` (any object with transformers'
+    `batch_decode(ids, skip_special_tokens=True)` or `decode`; loaded by the caller from a local directory —
+    nothing is fetched here). `images`: a pixel tensor [B, 3, S, S] / [3, S, S], a PIL image, or a list of PIL
+    images / uint8 HWC arrays. The model takes at most 32 rows per call (32 // num_beams images): larger
+    batches run in chunks whose rows are padded with pad_token_id to one width."""
 
-    def __init__(self, model: BlipForConditionalGeneration, tokenizer=None, max_new_tokens=20, use_graph=True):
+    def __init__(self, model: BlipForConditionalGeneration, tokenizer=None, max_new_tokens=20, use_graph=True,
+                 num_beams=1, length_penalty=1.0, early_stopping=False):
         self.model = model.eval()
         self.tokenizer = tokenizer
         self.max_new_tokens, self.use_graph = int(max_new_tokens), bool(use_graph)
+        self.num_beams, self.length_penalty, self.early_stopping = int(num_beams), float(length_penalty), early_stopping
+        self._pre = None
+
+    def pixels(self, images):
+        """images -> the model's pixel tensor [B, 3, S, S]"""
+        if isinstance(images, torch.Tensor):
+            return images[None] if images.dim() == 3 else images
+        if not isinstance(images, (list, tuple)):
+            images = [images]
+        if self._pre is None:
+            from .preprocess import ImagePreprocessor
+            dev = next(self.model.parameters()).device
+            self._pre = ImagePreprocessor("blip", device=dev, size=self.model.config.vision.image_size)
+        return self._pre(list(images))
 
     @torch.no_grad()
     def generate_ids(self, pixel_values, input_ids=None):
-        px = torch.as_tensor(pixel_values)
-        if px.dim() == 3:
-            px = px[None]
-        return self.model.generate(px, input_ids=input_ids, max_new_tokens=self.max_new_tokens,
-                                   use_graph=self.use_graph)
+        px = self.pixels(pixel_values)
+        kw = dict(input_ids=input_ids, max_new_tokens=self.max_new_tokens, use_graph=self.use_graph)
+        if self.num_beams != 1:
+            kw.update(num_beams=self.num_beams, length_penalty=self.length_penalty, early_stopping=self.early_stopping)
+        chunk = max(1, 32 // max(1, self.num_beams))
+        if px.shape[0] <= chunk:
+            return self.model.generate(px, **kw)
+        outs = [self.model.generate(px[i:i + chunk], **kw) for i in range(0, px.shape[0], chunk)]
+        width = max(o.shape[1] for o in outs)
+        pad = self.model.config.text.pad_token_id
+        return torch.cat([torch.nn.functional.pad(o, (0, width - o.shape[1]), value=pad) for o in outs], 0)
 
     def caption(self, pixel_values, input_ids=None):
         if self.tokenizer is None:

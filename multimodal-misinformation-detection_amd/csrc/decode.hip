@@ -5,6 +5,8 @@
 //                        16-byte loads, the dot products over D in registers, softmax statistics by wave
 //                        shuffles, no MFMA; the key range is split over waves when B*H alone leaves the
 //                        chip idle, and a second kernel combines the splits.
+//                        mmfd_attn_decode_grouped: the same with `group` query rows per row of k / v (the beams
+//                        of an image, csrc/beam.hip).
 //   mmfd_lm_head_argmax  argmax_v (x . W[v] + bias[v]) for B <= 32 rows without the [B, V] logits ever
 //                        being written: each workgroup streams one slab of vocabulary rows once for all B
 //                        rows and leaves one (max, index) per row; a second kernel reduces those.
@@ -71,6 +73,7 @@ struct DecodeParams {
   const void* q; const void* k; const void* v; void* o; float* ws;
   int64_t q_sb, k_sb, k_st, v_sb, v_st, o_sb;
   int B, H, Lk, S, chunk;   // S splits of `chunk` keys (a multiple of 64) each
+  int group;                // query rows per row of k / v (GROUPED kernels only; beam search: the beams of an image)
   float scale_log2;         // scale * log2(e): the softmax runs on exp2
 };
 
@@ -79,7 +82,9 @@ constexpr int DEC_WAVES = 4;  // independent (b, h, split) items per 256-thread 
 // one wave per (b, h, split): lane l takes keys k0 + l, k0 + l + 64, ... with its own running (max, sum,
 // accumulator); the lanes are merged once at the end. S == 1 writes o, else the unnormalised partial
 // {max, sum, acc[D]} goes to ws[(b*H + h)*S + split].
-template <typename T, int D> __global__ __launch_bounds__(64 * DEC_WAVES) void attn_decode_kernel(DecodeParams p) {
+// GROUPED: query row b reads the keys and values of row b / group (the instantiation without it is the code it was).
+template <typename T, int D, bool GROUPED = false>
+__global__ __launch_bounds__(64 * DEC_WAVES) void attn_decode_kernel(DecodeParams p) {
   constexpr int E = Chunk<T>::E;
   const int lane = threadIdx.x & 63;
   const int64_t item = (int64_t)blockIdx.x * DEC_WAVES + (threadIdx.x >> 6);
@@ -102,8 +107,9 @@ template <typename T, int D> __global__ __launch_bounds__(64 * DEC_WAVES) void a
 #pragma unroll
   for (int d = 0; d < D; ++d) acc[d] = 0.f;
   float m = -INFINITY, l = 0.f;
-  const T* kb = (const T*)p.k + b * p.k_sb + (int64_t)h * D;
-  const T* vb = (const T*)p.v + b * p.v_sb + (int64_t)h * D;
+  const int kv_row = GROUPED ? b / p.group : b;
+  const T* kb = (const T*)p.k + kv_row * p.k_sb + (int64_t)h * D;
+  const T* vb = (const T*)p.v + kv_row * p.v_sb + (int64_t)h * D;
   for (int key = k0 + lane; key < k1; key += 64) {  // rows at and past Lk are never read
     const T* kr = kb + (int64_t)key * p.k_st;
     float s0 = 0.f, s1 = 0.f;
@@ -399,10 +405,11 @@ extern "C" int64_t mmfd_attn_decode_workspace_bytes(int64_t B, int64_t H, int64_
   return S > 1 ? B * H * S * (D + 2) * (int64_t)sizeof(float) : 0;
 }
 
-extern "C" int mmfd_attn_decode(int dtype, int64_t B, int64_t H, int64_t D, int64_t Lk, float scale, const void* q,
-                                int64_t q_sb, const void* k, int64_t k_sb, int64_t k_st, const void* v, int64_t v_sb,
-                                int64_t v_st, void* o, int64_t o_sb, void* workspace, int64_t workspace_bytes,
-                                mmfd_stream_t stream) {
+namespace {
+int attn_decode_impl(int dtype, int64_t B, int64_t group, int64_t H, int64_t D, int64_t Lk, float scale, const void* q,
+                     int64_t q_sb, const void* k, int64_t k_sb, int64_t k_st, const void* v, int64_t v_sb,
+                     int64_t v_st, void* o, int64_t o_sb, void* workspace, int64_t workspace_bytes,
+                     mmfd_stream_t stream) {
   MMFD_CHECK_ARG(dtype == MMFD_F32 || dtype == MMFD_BF16, "mmfd_attn_decode: bad dtype");
   MMFD_CHECK_ARG(D == 32 || D == 64, "mmfd_attn_decode: head_dim %lld unsupported (32 or 64)", (long long)D);
   MMFD_CHECK_ARG(B >= 0 && H > 0 && B * H < (1 << 24), "mmfd_attn_decode: bad shape");
@@ -418,7 +425,7 @@ extern "C" int mmfd_attn_decode(int dtype, int64_t B, int64_t H, int64_t D, int6
   DecodeParams p;
   p.q = q; p.k = k; p.v = v; p.o = o; p.ws = (float*)workspace;
   p.q_sb = q_sb; p.k_sb = k_sb; p.k_st = k_st; p.v_sb = v_sb; p.v_st = v_st; p.o_sb = o_sb;
-  p.B = (int)B; p.H = (int)H; p.Lk = (int)Lk;
+  p.B = (int)B; p.H = (int)H; p.Lk = (int)Lk; p.group = (int)group;
   decode_plan(B, H, Lk, p.S, p.chunk);
   p.scale_log2 = scale * 1.4426950408889634f;
   if (p.S > 1) {
@@ -430,7 +437,15 @@ extern "C" int mmfd_attn_decode(int dtype, int64_t B, int64_t H, int64_t D, int6
   hipStream_t s = (hipStream_t)stream;
   const int64_t items = B * H * p.S;
   const dim3 grid((unsigned)((items + DEC_WAVES - 1) / DEC_WAVES)), block(64 * DEC_WAVES);
-  if (dtype == MMFD_F32) {
+  if (group > 1) {
+    if (dtype == MMFD_F32) {
+      if (D == 64) hipLaunchKernelGGL((attn_decode_kernel<float, 64, true>), grid, block, 0, s, p);
+      else hipLaunchKernelGGL((attn_decode_kernel<float, 32, true>), grid, block, 0, s, p);
+    } else {
+      if (D == 64) hipLaunchKernelGGL((attn_decode_kernel<bf16, 64, true>), grid, block, 0, s, p);
+      else hipLaunchKernelGGL((attn_decode_kernel<bf16, 32, true>), grid, block, 0, s, p);
+    }
+  } else if (dtype == MMFD_F32) {
     if (D == 64) hipLaunchKernelGGL((attn_decode_kernel<float, 64>), grid, block, 0, s, p);
     else hipLaunchKernelGGL((attn_decode_kernel<float, 32>), grid, block, 0, s, p);
   } else {
@@ -446,6 +461,25 @@ extern "C" int mmfd_attn_decode(int dtype, int64_t B, int64_t H, int64_t D, int6
     MMFD_CHECK_LAUNCH("mmfd_attn_decode (combine)");
   }
   return 0;
+}
+}  // namespace
+
+extern "C" int mmfd_attn_decode(int dtype, int64_t B, int64_t H, int64_t D, int64_t Lk, float scale, const void* q,
+                                int64_t q_sb, const void* k, int64_t k_sb, int64_t k_st, const void* v, int64_t v_sb,
+                                int64_t v_st, void* o, int64_t o_sb, void* workspace, int64_t workspace_bytes,
+                                mmfd_stream_t stream) {
+  return attn_decode_impl(dtype, B, 1, H, D, Lk, scale, q, q_sb, k, k_sb, k_st, v, v_sb, v_st, o, o_sb, workspace,
+                          workspace_bytes, stream);
+}
+
+extern "C" int mmfd_attn_decode_grouped(int dtype, int64_t B, int64_t group, int64_t H, int64_t D, int64_t Lk,
+                                        float scale, const void* q, int64_t q_sb, const void* k, int64_t k_sb,
+                                        int64_t k_st, const void* v, int64_t v_sb, int64_t v_st, void* o, int64_t o_sb,
+                                        void* workspace, int64_t workspace_bytes, mmfd_stream_t stream) {
+  MMFD_CHECK_ARG(group >= 1 && group <= 64 && B % group == 0,
+                 "mmfd_attn_decode_grouped: %lld query rows in groups of %lld", (long long)B, (long long)group);
+  return attn_decode_impl(dtype, B, group, H, D, Lk, scale, q, q_sb, k, k_sb, k_st, v, v_sb, v_st, o, o_sb, workspace,
+                          workspace_bytes, stream);
 }
 
 extern "C" int64_t mmfd_lm_head_argmax_workspace_bytes(int dtype, int64_t B, int64_t V, int64_t K) {

@@ -210,10 +210,17 @@ SIGNATURES = {
     "mmfd_attn_decode_workspace_bytes": (_I64, [_I64, _I64, _I64, _I64]),
     "mmfd_attn_decode": (_I, [_I, _I64, _I64, _I64, _I64, _F, _VP, _I64, _VP, _I64, _I64, _VP, _I64, _I64, _VP, _I64,
                               _VP, _I64, _VP]),
+    "mmfd_attn_decode_grouped": (_I, [_I, _I64, _I64, _I64, _I64, _I64, _F, _VP, _I64, _VP, _I64, _I64, _VP, _I64, _I64, _VP,
+                                      _I64, _VP, _I64, _VP]),
     "mmfd_lm_head_argmax_workspace_bytes": (_I64, [_I, _I64, _I64, _I64]),
     "mmfd_lm_head_argmax_slab": (_I64, [_I, _I64, _I64, _I64]),
     "mmfd_lm_head_argmax": (_I, [_I, _I64, _I64, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _VP, _I64, _VP, _I64, _VP]),
     "mmfd_greedy_select": (_I, [_I64, _VP, _VP, _I64, _VP, _I64, _I64, _VP, _I64, _VP]),
+    "mmfd_beam_select_slab": (_I64, [_I64]),
+    "mmfd_beam_select_workspace_bytes": (_I64, [_I64, _I64, _I64]),
+    "mmfd_beam_select": (_I, [_I64, _I64, _I64, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
+    "mmfd_beam_update": (_I, [_I64, _I64, _I64, _I64, _I64, _I, _I, _I64, _F] + [_VP] * 12 + [_I64, _VP]),
+    "mmfd_beam_reorder": (_I, [_I64, _I64, _I64, _I64, _I64, _VP, _VP, _VP, _VP]),
 }
 
 _lib = None
@@ -1451,10 +1458,11 @@ def attn_decode_splits(B, H, Lk):
     return s
 
 
-def attn_decode(q, k, v, H, Lk, *, scale=None, out=None, workspace=None):
+def attn_decode(q, k, v, H, Lk, *, scale=None, out=None, workspace=None, group=1):
     """single-token attention: q [B, H*D], k / v [B, Lmax, H*D] (views into a packed cache are fine), keys
     0 .. Lk-1 only (rows past Lk are never read); returns o [B, H*D]. `workspace`: a uint8 tensor of
-    mmfd_attn_decode_workspace_bytes (allocated here when the key range is split and none is given)."""
+    mmfd_attn_decode_workspace_bytes (allocated here when the key range is split and none is given).
+    group > 1: k / v hold B / group rows and query row b attends row b // group (the beams of an image)."""
     _require_cuda(q, k, v, out, workspace)
     if q.dim() != 2 or k.dim() != 3 or v.dim() != 3 or q.stride(1) != 1 or k.stride(2) != 1 or v.stride(2) != 1:
         raise ValueError("attn_decode: q [B, H*D] and k / v [B, Lmax, H*D] views with a contiguous last dim")
@@ -1462,6 +1470,9 @@ def attn_decode(q, k, v, H, Lk, *, scale=None, out=None, workspace=None):
         raise TypeError("attn_decode: q, k, v must share a dtype")
     B, HD = q.shape
     D = HD // H
+    group = int(group)
+    if group != 1 and (group < 1 or B % group or k.shape[0] * group != B or v.shape[0] * group != B):
+        raise ValueError(f"attn_decode: {B} query rows in groups of {group} need {B // max(group, 1)} rows of k / v")
     if Lk > k.shape[1] or Lk > v.shape[1]:
         raise ValueError(f"attn_decode: Lk = {Lk} exceeds the cache rows ({k.shape[1]})")
     if out is None:
@@ -1471,11 +1482,14 @@ def attn_decode(q, k, v, H, Lk, *, scale=None, out=None, workspace=None):
     need = lib().mmfd_attn_decode_workspace_bytes(B, H, D, int(Lk)) if B and Lk > 0 and D > 0 else 0
     if need > 0 and (workspace is None or workspace.numel() * workspace.element_size() < need):
         workspace = torch.empty(need, device=q.device, dtype=torch.uint8)
-    _check(lib().mmfd_attn_decode(dtype_code(q.dtype), B, H, D, int(Lk), float(scale if scale is not None else D ** -0.5),
-                                  _ptr(q), q.stride(0), _ptr(k), k.stride(0), k.stride(1), _ptr(v), v.stride(0),
-                                  v.stride(1), _ptr(out), out.stride(0), _ptr(workspace),
-                                  workspace.numel() * workspace.element_size() if workspace is not None else 0,
-                                  _stream()), "mmfd_attn_decode")
+    tail = (float(scale if scale is not None else D ** -0.5), _ptr(q), q.stride(0), _ptr(k), k.stride(0), k.stride(1),
+            _ptr(v), v.stride(0), v.stride(1), _ptr(out), out.stride(0), _ptr(workspace),
+            workspace.numel() * workspace.element_size() if workspace is not None else 0, _stream())
+    if group == 1:
+        _check(lib().mmfd_attn_decode(dtype_code(q.dtype), B, H, D, int(Lk), *tail), "mmfd_attn_decode")
+    else:
+        _check(lib().mmfd_attn_decode_grouped(dtype_code(q.dtype), B, group, H, D, int(Lk), *tail),
+               "mmfd_attn_decode_grouped")
     return out
 
 
@@ -1532,3 +1546,117 @@ def greedy_select(argmax, finished, eos, pad, next_tokens, forced=None):
                                     _ptr(finished), int(eos), int(pad), _ptr(next_tokens), next_tokens.stride(0),
                                     _stream()), "mmfd_greedy_select")
     return next_tokens
+
+
+# ------------------------------------------------------------------------------------------------
+# beam search (csrc/beam.hip)
+# ------------------------------------------------------------------------------------------------
+def beam_select_slab(V):
+    """vocabulary entries per workgroup of beam_select"""
+    s = lib().mmfd_beam_select_slab(int(V))
+    _check(0 if s > 0 else MMFD_ERR_INVALID, "mmfd_beam_select_slab")
+    return int(s)
+
+
+def beam_select_workspace_bytes(B, nb, V):
+    n = lib().mmfd_beam_select_workspace_bytes(int(B), int(nb), int(V))
+    _check(0 if n > 0 else MMFD_ERR_INVALID, "mmfd_beam_select_workspace_bytes")
+    return int(n)
+
+
+def _i32(t, shape, what):
+    if t.dtype != torch.int32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous int32 tensor of shape {tuple(shape)}")
+
+
+def _f32(t, shape, what):
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous fp32 tensor of shape {tuple(shape)}")
+
+
+def beam_select(logits, running, nb, *, out=None, workspace=None):
+    """per image the 2 nb best (score, beam, token) of its nb * V candidates, score = log_softmax(logits[row])
+    + running[row]: logits fp32 [B * nb, V] (rows may be strided), running fp32 [B * nb]. Returns (score fp32,
+    beam int32, token int32), each [B, 2 nb], best first; equal scores go to the lower beam, then the lower
+    token, and a NaN is never chosen over a number."""
+    _require_cuda(logits, running, workspace)
+    nb = int(nb)
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1 or nb < 1 or logits.shape[0] % nb:
+        raise ValueError("beam_select: logits must be an fp32 [B * nb, V] view with a contiguous last dim")
+    R, V = logits.shape
+    B = R // nb
+    _f32(running, (R,), "beam_select: running")
+    if out is None:
+        out = (torch.empty(B, 2 * nb, device=logits.device), torch.empty(B, 2 * nb, device=logits.device, dtype=torch.int32),
+               torch.empty(B, 2 * nb, device=logits.device, dtype=torch.int32))
+    _f32(out[0], (B, 2 * nb), "beam_select: out score")
+    _i32(out[1], (B, 2 * nb), "beam_select: out beam")
+    _i32(out[2], (B, 2 * nb), "beam_select: out token")
+    _require_cuda(*out)
+    if workspace is None:
+        workspace = torch.empty(beam_select_workspace_bytes(B, nb, V), device=logits.device, dtype=torch.uint8)
+    _check(lib().mmfd_beam_select(B, nb, V, _ptr(logits), logits.stride(0), _ptr(running), _ptr(out[0]), _ptr(out[1]),
+                                  _ptr(out[2]), _ptr(workspace), workspace.numel() * workspace.element_size(),
+                                  _stream()), "mmfd_beam_select")
+    return out
+
+
+def beam_update(cand, state, t, n_forced, last, eos, length_penalty, early_stopping, next_tokens):
+    """one beam step on the device state `state` (dict: run_score, fin_score fp32 [B, nb]; fin_flag, fin_len int32
+    [B, nb]; run_seq, fin_seq int32 [B, nb, T]; flags int32 [B, 4]; parent int32 [B * nb]) from the candidates
+    `cand` of beam_select: the step that embedded position t chooses position t + 1 (include/mmfd.h
+    mmfd_beam_update). next_tokens: int64 [B * nb] view receiving the token of every new beam."""
+    B, nb, T = state["run_seq"].shape
+    _require_cuda(*cand, next_tokens, *(state[k] for k in ("run_score", "fin_score", "fin_flag", "fin_len", "run_seq",
+                                                             "fin_seq", "flags", "parent")))
+    _f32(cand[0], (B, 2 * nb), "beam_update: candidate scores")
+    _i32(cand[1], (B, 2 * nb), "beam_update: candidate beams")
+    _i32(cand[2], (B, 2 * nb), "beam_update: candidate tokens")
+    _f32(state["run_score"], (B, nb), "beam_update: run_score")
+    _f32(state["fin_score"], (B, nb), "beam_update: fin_score")
+    _i32(state["fin_flag"], (B, nb), "beam_update: fin_flag")
+    _i32(state["fin_len"], (B, nb), "beam_update: fin_len")
+    _i32(state["run_seq"], (B, nb, T), "beam_update: run_seq")
+    _i32(state["fin_seq"], (B, nb, T), "beam_update: fin_seq")
+    _i32(state["flags"], (B, 4), "beam_update: flags")
+    _i32(state["parent"], (B * nb,), "beam_update: parent")
+    if next_tokens.dtype != torch.int64 or next_tokens.dim() != 1 or next_tokens.numel() != B * nb:
+        raise ValueError("beam_update: next_tokens must be an int64 [B * nb] view")
+    gen_len = int(t) + 1 - int(n_forced)
+    if gen_len < 1:
+        raise ValueError("beam_update: a forced step has no beam update")
+    _check(lib().mmfd_beam_update(B, nb, T, int(t), gen_len, int(bool(last)), int(bool(early_stopping)), int(eos),
+                                  float(float(gen_len) ** float(length_penalty)), _ptr(cand[0]), _ptr(cand[1]),
+                                  _ptr(cand[2]), _ptr(state["run_score"]), _ptr(state["fin_score"]),
+                                  _ptr(state["fin_flag"]), _ptr(state["fin_len"]), _ptr(state["run_seq"]),
+                                  _ptr(state["fin_seq"]), _ptr(state["flags"]), _ptr(state["parent"]),
+                                  _ptr(next_tokens), next_tokens.stride(0), _stream()), "mmfd_beam_update")
+
+
+def ptr_table(tensors):
+    """int64 device tensor of the tensors' addresses (the `src` / `dst` of beam_reorder)"""
+    _require_cuda(*tensors)
+    return torch.tensor([t.data_ptr() for t in tensors], dtype=torch.int64, device=tensors[0].device)
+
+
+def beam_reorder(src, dst, src_table, dst_table, parent, beam_rows, n_pos):
+    """dst[l][r, :n_pos] = src[l][parent[r], :n_pos] for r < beam_rows (the other rows copy themselves), all
+    layers in one launch. src / dst: lists of equally shaped contiguous [rows, steps, width] caches whose
+    addresses src_table / dst_table (ptr_table) hold; positions at and past n_pos are not touched."""
+    _require_cuda(src_table, dst_table, parent)
+    a = src[0]
+    rows, steps, width = a.shape
+    for s, d in zip(src, dst):
+        if (s.shape != a.shape or d.shape != a.shape or s.dtype != a.dtype or d.dtype != a.dtype or not s.is_contiguous()
+                or not d.is_contiguous() or s.data_ptr() == d.data_ptr()):
+            raise ValueError("beam_reorder: src / dst must be distinct contiguous caches of one shape and dtype")
+    if len(src) != len(dst) or src_table.numel() != len(src) or dst_table.numel() != len(dst) \
+            or src_table.dtype != torch.int64 or dst_table.dtype != torch.int64:
+        raise ValueError("beam_reorder: one int64 address per layer")
+    if not 0 <= int(n_pos) <= steps:
+        raise ValueError(f"beam_reorder: n_pos = {n_pos} exceeds the cache rows ({steps})")
+    if parent.dtype != torch.int32 or parent.numel() < int(beam_rows) or not parent.is_contiguous():
+        raise ValueError("beam_reorder: parent must be a contiguous int32 vector of at least beam_rows entries")
+    es = a.element_size()
+    _check(lib().mmfd_beam_reorder(len(src), rows, int(beam_rows), steps * width * es, int(n_pos) * width * es,
+                                   _ptr(src_table), _ptr(dst_table), _ptr(parent), _stream()), "mmfd_beam_reorder")

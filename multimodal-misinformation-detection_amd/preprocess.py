@@ -8,9 +8,13 @@ fp32 NCHW pixel tensor, bit-identical to the reference's torchvision transforms 
     Resize((224, 224)), ToTensor, Normalize(ImageNet mean / std);
   * mode "evaluate": MisinformationPredictor's image_transform of evaluate.py:71-79 —
     Resize((256, 256)), ToTensor, Normalize(ImageNet mean / std).
+  * mode "blip": transformers' BlipImageProcessor as the captioning stage calls it
+    (src/preprocess/caption.py:25-28, `processor(image, return_tensors="pt")`) — a straight resize to
+    (384, 384) with PIL's BICUBIC filter, rescale by 1/255, Normalize(OpenAI CLIP mean / std).
 `size=` overrides the (square) resize of the fixed-size modes, e.g. 224 for a ViT-B/16 predictor.
 
-torchvision resizes PIL images with PIL's Image.resize(BILINEAR). Its taps are computed here on the
+torchvision resizes PIL images with PIL's Image.resize(BILINEAR). Its taps (and the bicubic ones of mode
+"blip") are computed here on the
 host exactly as PIL computes them (double precision, 22-bit fixed point; cached per (in, out)
 size), and csrc/preprocess.hip runs PIL's integer two-pass arithmetic on the device, then ToTensor's
 division and Normalize's subtract/divide in fp32. JPEG/PNG decoding stays on the host (PIL).
@@ -28,10 +32,14 @@ from . import kernels as K
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
+OPENAI_CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
+OPENAI_CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 MODES = {
     "train": dict(resize=256, crop=256, mean=(0.5, 0.5, 0.5), std=IMAGENET_STD),   # dataset.py:14-19
     "retrieval": dict(resize=(224, 224), crop=None, mean=IMAGENET_MEAN, std=IMAGENET_STD),  # im2im:19-27
     "evaluate": dict(resize=(256, 256), crop=None, mean=IMAGENET_MEAN, std=IMAGENET_STD),   # evaluate.py:71-79
+    "blip": dict(resize=(384, 384), crop=None, mean=OPENAI_CLIP_MEAN, std=OPENAI_CLIP_STD,  # caption.py:25-28
+                 filter="bicubic"),
 }
 _PB = 22  # PIL PRECISION_BITS (8-bit images)
 
@@ -43,13 +51,32 @@ class ImageDesc(ctypes.Structure):
                 ("kx_size", ctypes.c_int32), ("ky_size", ctypes.c_int32), ("tmp_off", ctypes.c_int64)]
 
 
+def _bilinear_filter(t):
+    return 1.0 - t if t < 1.0 else 0.0
+
+
+def _bicubic_filter(t, a=-0.5):
+    """PIL's bicubic_filter (Resample.c): the Keys kernel with a = -0.5"""
+    if t < 1.0:
+        return ((a + 2.0) * t - (a + 3.0)) * t * t + 1
+    if t < 2.0:
+        return (((t - 5) * t + 8) * t - 4) * a
+    return 0.0
+
+
+_FILTERS = {"bilinear": (_bilinear_filter, 1.0), "bicubic": (_bicubic_filter, 2.0)}  # (weight, support)
+
+
 @functools.lru_cache(maxsize=4096)
-def pil_taps(in_size: int, out_size: int):
-    """PIL's precompute_coeffs + normalize_coeffs_8bpc for the bilinear filter over the whole input
-    range: int32 [out_size, K + 2] records [xmin, n, k_0 .. k_{K-1}] (K = 2 ceil(support) + 1)."""
+def pil_taps(in_size: int, out_size: int, filter: str = "bilinear"):
+    """PIL's precompute_coeffs + normalize_coeffs_8bpc for the bilinear (default) or bicubic filter over the
+    whole input range: int32 [out_size, K + 2] records [xmin, n, k_0 .. k_{K-1}] (K = 2 ceil(support) + 1)."""
+    if filter not in _FILTERS:
+        raise ValueError(f"filter must be one of {list(_FILTERS)}")
+    weight, base_support = _FILTERS[filter]
     scale = in_size / out_size
     fs = max(scale, 1.0)
-    support = 1.0 * fs
+    support = base_support * fs
     K_ = int(math.ceil(support)) * 2 + 1
     out = np.zeros((out_size, K_ + 2), np.int32)
     ss = 1.0 / fs
@@ -60,8 +87,7 @@ def pil_taps(in_size: int, out_size: int):
         w = []
         ww = 0.0
         for x in range(xmax):
-            t = abs((x + xmin - center + 0.5) * ss)
-            v = 1.0 - t if t < 1.0 else 0.0
+            v = weight(abs((x + xmin - center + 0.5) * ss))
             w.append(v)
             ww += v
         out[xx, 0], out[xx, 1] = xmin, xmax
@@ -106,6 +132,7 @@ class ImagePreprocessor:
         if mode not in MODES:
             raise ValueError(f"mode must be one of {list(MODES)}")
         self.mode, self.cfg, self.device = mode, dict(MODES[mode]), torch.device(device)
+        self.filter = self.cfg.pop("filter", "bilinear")
         if size is not None:
             if self.cfg["crop"]:
                 raise ValueError("size= applies to the fixed-size modes (retrieval / evaluate)")
@@ -126,7 +153,8 @@ class ImagePreprocessor:
             cy, cx = center_crop_origin(oh, ow, self.cfg["crop"]) if self.cfg["crop"] else (0, 0)
             if cy < 0 or cx < 0:
                 raise ValueError("image smaller than the crop after resizing")
-            tx, ty = pil_taps(w, ow), pil_taps(h, oh)
+            tx, ty = (pil_taps(w, ow), pil_taps(h, oh)) if self.filter == "bilinear" else \
+                (pil_taps(w, ow, self.filter), pil_taps(h, oh, self.filter))
             d = descs[i]
             d.src = int(src_ptrs[i])
             d.h, d.w, d.stride = h, w, 3 * w

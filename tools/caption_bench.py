@@ -1,12 +1,14 @@
 """Times greedy BLIP captioning (mmfd.blip) at the default configuration (blip-image-captioning-large
 shapes, random weights and pixels) and the LM-head kernel alone.
 
-  python tools/caption_bench.py [--batches 1 20] [--reps 3] [--out FILE]
+  python tools/caption_bench.py [--batches 1 20] [--num-beams 1] [--reps 3] [--out FILE]
 
 Per (batch, precision): wall time of `generate` (20 new tokens; host-synchronised, the ids copied back)
 eager and as one graph replay, and per precision the device time of kernels.lm_head_argmax at
 V = 30524, K = 768 with the bytes it has to read (W + bias + x) per second. Prints one JSON line.
-Random weights seldom produce the stop token, so eager mode runs all 20 steps like the graph."""
+Random weights seldom produce the stop token, so eager mode runs all 20 steps like the graph.
+--num-beams N > 1 times beam search instead (batch * N decoder rows) and, per precision and batch, the device time
+of one step's three beam kernel groups (selection, update, cache reorder at position 10) on the model's shapes."""
 import argparse
 import json
 import os
@@ -57,9 +59,45 @@ def lm_head_rate(dtype, B, V=30524, Kd=768, reps=20):
             "note": "both launches (partials + final reduce) between the events; cold = after a 512 MiB fill"}
 
 
+def beam_step_times(dt, B, nb, V=30524, E=768, L=12, steps=20, t=10, reps=20):
+    """device time (us, median of reps, each between two events) of the three kernel groups of one beam step on
+    random state: the selection over [B * nb, V] logits, the update, and the reorder of L caches up to position t"""
+    R, T, dev = B * nb, steps + 1, "cuda"
+    i32 = dict(dtype=torch.int32, device=dev)
+    logits = torch.randn(R, V, device=dev)
+    st = dict(run_score=-torch.rand(B, nb, device=dev), fin_score=torch.full((B, nb), -1e9, device=dev),
+              fin_flag=torch.zeros(B, nb, **i32), fin_len=torch.zeros(B, nb, **i32), run_seq=torch.zeros(B, nb, T, **i32),
+              fin_seq=torch.zeros(B, nb, T, **i32), flags=torch.ones(B, 4, **i32), parent=torch.zeros(R, **i32))
+    cand = K.beam_select(logits, st["run_score"].view(-1), nb)
+    ws = torch.empty(K.beam_select_workspace_bytes(B, nb, V), dtype=torch.uint8, device=dev)
+    nxt = torch.zeros(R, dtype=torch.int64, device=dev)
+    Bp = max(R, 16)
+    kv = [[torch.zeros(Bp, steps, 2 * E, device=dev, dtype=dt) for _ in range(L)] for _ in range(2)]
+    tab = [K.ptr_table(kv[0]), K.ptr_table(kv[1])]
+    groups = {
+        "select_us": lambda: K.beam_select(logits, st["run_score"].view(-1), nb, out=cand, workspace=ws),
+        "update_us": lambda: K.beam_update(cand, st, t, 0, False, 102, 1.0, False, nxt),
+        "reorder_us": lambda: K.beam_reorder(kv[0], kv[1], tab[0], tab[1], st["parent"], R, t + 1),
+    }
+    out = {"B": B, "num_beams": nb, "position": t}
+    for name, fn in groups.items():
+        fn()
+        ts = []
+        for _ in range(reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1) * 1e3)
+        out[name] = round(sorted(ts)[len(ts) // 2], 1)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 20])
+    ap.add_argument("--num-beams", type=int, default=1)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -67,22 +105,28 @@ def main():
     m = BlipForConditionalGeneration().to("cuda").eval()
     for p in m.parameters():
         p.requires_grad_(False)
-    res = {"generate": [], "lm_head": []}
+    nb = a.num_beams
+    gen = (lambda px, g: m.generate(px, use_graph=g)) if nb == 1 else \
+        (lambda px, g: m.generate(px, use_graph=g, num_beams=nb))
+    res = {"generate": [], "lm_head": [], "num_beams": nb, "beam_step": []}
     for prec, dt in (("fp32", torch.float32), ("bf16", torch.bfloat16)):
         m.set_precision(prec)
         for B in a.batches:
             px = torch.randn(B, 3, 384, 384, device="cuda")
-            row = {"precision": prec, "B": B}
+            row = {"precision": prec, "B": B, "rows": B * nb}
             for mode, g in (("eager", False), ("graph", True)):
-                t_min, t_med = wall(lambda: m.generate(px, use_graph=g), a.reps)
+                t_min, t_med = wall(lambda: gen(px, g), a.reps)
                 row[mode + "_ms"] = round(t_med, 2)
                 row[mode + "_ms_per_image"] = round(t_med / B, 2)
                 row[mode + "_ms_min"] = round(t_min, 2)
-            row["tokens"] = int(m.generate(px, use_graph=True).shape[1]) - 1
+            row["tokens"] = int(gen(px, True).shape[1]) - 1
             res["generate"].append(row)
             print(row, file=sys.stderr, flush=True)
-            res["lm_head"].append(dict(lm_head_rate(dt, B), precision=prec))
+            res["lm_head"].append(dict(lm_head_rate(dt, B * nb), precision=prec))
             print(res["lm_head"][-1], file=sys.stderr, flush=True)
+            if nb > 1:
+                res["beam_step"].append(dict(beam_step_times(dt, B, nb), precision=prec))
+                print(res["beam_step"][-1], file=sys.stderr, flush=True)
         m.invalidate_caches()
     line = json.dumps(res)
     print(line)
