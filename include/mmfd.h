@@ -36,8 +36,11 @@ enum {
   MMFD_ACT_RELU = 2,      /* nn.ReLU() (model.py:264 ...) */
   MMFD_ACT_GELU_BWD = 3,  /* out *= gelu'(aux)  (aux = saved pre-activation) */
   MMFD_ACT_RELU_BWD = 4,  /* out *= (aux > 0)   */
-  MMFD_ACT_TANH = 5,      /* tanh (HF BertPooler, the cross-encoder's [CLS] pooler), forward only */
-  MMFD_ACT_SIGMOID = 6,   /* 1 / (1 + exp(-x)) (CrossEncoder's default score activation) */
+  MMFD_ACT_TANH = 5,      /* tanh (HF BertPooler, the cross-encoder's [CLS] pooler), forward only; on the
+                             MFMA paths it runs in the split-K reduce and needs a workspace of
+                             mmfd_gemm_workspace_bytes() bytes (MMFD_ERR_INVALID without one) */
+  MMFD_ACT_SIGMOID = 6,   /* 1 / (1 + exp(-x)) (CrossEncoder's default score activation); needs the
+                             workspace as MMFD_ACT_TANH does */
   MMFD_ACT_GELU_D = 7,    /* GELU as MMFD_ACT_GELU, but aux <- gelu'(pre-activation) (training forward) */
   MMFD_ACT_MUL_AUX = 8    /* out *= aux  (aux = a saved derivative: the MMFD_ACT_GELU_D backward) */
 };
@@ -87,9 +90,10 @@ typedef struct mmfd_epilogue {
    im2im_retrieval.py:14-17, 29-36): A is the NHWC activation x[N][H][W][C] and
      op(A)[m][k] = x[n][oh*stride - pad + kh][ow*stride - pad + kw][c]   (0 outside the image)
    with m = (n*Ho + oh)*Wo + ow, k = (kh*KW + kw)*C + c — the im2col matrix, gathered by the GEMM's
-   operand fill instead of being written. Requires trans_a = 0, M = N*Ho*Wo, K = KH*KW*C, C a
-   multiple of 32 (fp32) / 64 (bf16), x 16-B aligned, no a_rowsum; lda is ignored. With fp32
-   operands on the split-operand path a_planes, when given, are the planes [3][N*H*W][C] of x. */
+   operand fill instead of being written. Requires trans_a = 0 and trans_b = 0 (B is the [N][K]
+   weight), M = N*Ho*Wo, K = KH*KW*C, C a multiple of 32 (fp32) / 64 (bf16), x 16-B aligned, no
+   a_rowsum; lda is ignored. With fp32 operands on the split-operand path a_planes, when given, are
+   the planes [3][N*H*W][C] of x. */
 typedef struct mmfd_conv_geom {
   int64_t N, H, W, C;      /* input images */
   int KH, KW, stride, pad;

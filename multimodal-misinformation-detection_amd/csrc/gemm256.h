@@ -350,30 +350,18 @@ G8_KERNEL(gemm256_kernel, true)
 G8_KERNEL(gemm256_act_kernel, false)
 #undef G8_KERNEL
 
-int g8_group_m() {
-  static const int gm = getenv("MMFD_G8_GROUP_M") ? std::max(1, atoi(getenv("MMFD_G8_GROUP_M"))) : 1;
-  return gm;
-}
+int g8_group_m() { return mmfd_gemmx::g_gemm_sw.group_m; }
 
 template <typename T, int TA, int TB, typename TC, bool PRE, bool X6>
-void launch_g8_v(const mmfd_gemm_args& a, const EpiArgs& e, float* ws, int splits, int tps, float* rs_out,
-                 int rs_mode, hipStream_t s, const void* A, int64_t lda, const void* B, int64_t ldb, X6Args x6) {
-  dim3 grid((unsigned)((a.N + G8_BN - 1) / G8_BN), (unsigned)((a.M + G8_BM - 1) / G8_BM), (unsigned)splits);
-  static bool attr = [] {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<T, TA, TB, TC, PRE, X6>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS) == hipSuccess &&
-           hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_act_kernel<T, TA, TB, TC, PRE, X6>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS) == hipSuccess;
-  }();
-  (void)attr;
-  if (ws != nullptr || (e.act == MMFD_ACT_NONE && e.p <= 0.f))
-    hipLaunchKernelGGL((gemm256_kernel<T, TA, TB, TC, PRE, X6>), grid, dim3(NT), G8_LDS, s, (const T*)A, lda,
-                       (const T*)B, ldb, (TC*)a.C, a.ldc, ws, a.M, a.N, a.K, a.alpha, tps, e, rs_out,
-                       a.a_rowsum_beta, rs_mode, g8_group_m(), x6);
-  else
-    hipLaunchKernelGGL((gemm256_act_kernel<T, TA, TB, TC, PRE, X6>), grid, dim3(NT), G8_LDS, s, (const T*)A, lda,
-                       (const T*)B, ldb, (TC*)a.C, a.ldc, ws, a.M, a.N, a.K, a.alpha, tps, e, rs_out,
-                       a.a_rowsum_beta, rs_mode, g8_group_m(), x6);
+void launch_g8_v(const mmfd_gemm_args& a, const EpiArgs& e, const G8Launch& L, hipStream_t s) {
+#define G8_GO(KERNEL)                                                                                          \
+  lds_max<&KERNEL<T, TA, TB, TC, PRE, X6>>(G8_LDS);                                                           \
+  hipLaunchKernelGGL((KERNEL<T, TA, TB, TC, PRE, X6>), L.grid, dim3(NT), G8_LDS, s, (const T*)L.A, L.lda,      \
+                     (const T*)L.B, L.ldb, (TC*)a.C, a.ldc, L.ws, a.M, a.N, a.K, a.alpha, L.tps, e, L.rs_out, \
+                     a.a_rowsum_beta, L.rs_mode, g8_group_m(), L.x6)
+  if (L.form == mmfd_gemmx::G8_LEAN) { G8_GO(gemm256_kernel); }
+  else { G8_GO(gemm256_act_kernel); }
+#undef G8_GO
 }
 
 }  // namespace

@@ -16,24 +16,14 @@
 namespace mmfd_gemmx {
 
 template <typename T, int TA, int TB, bool X6>
-void launch_g8_f32out(const mmfd_gemm_args& a, const EpiArgs& e, float* ws, int splits, int tps, float* rs_out,
-                      int rs_mode, hipStream_t s, const void* A, int64_t lda, const void* B, int64_t ldb, X6Args x6) {
-  launch_g8_v<T, TA, TB, float, false, X6>(a, e, ws, splits, tps, rs_out, rs_mode, s, A, lda, B, ldb, x6);
+void launch_g8_f32out(const mmfd_gemm_args& a, const EpiArgs& e, const G8Launch& L, hipStream_t s) {
+  launch_g8_v<T, TA, TB, float, false, X6>(a, e, L, s);
 }
 
-#define MMFD_F32OUT(T, X6)                                                                                  \
-  template void launch_g8_f32out<T, 0, 0, X6>(const mmfd_gemm_args&, const EpiArgs&, float*, int, int, float*, \
-                                              int, hipStream_t, const void*, int64_t, const void*, int64_t,   \
-                                              X6Args);                                                        \
-  template void launch_g8_f32out<T, 0, 1, X6>(const mmfd_gemm_args&, const EpiArgs&, float*, int, int, float*, \
-                                              int, hipStream_t, const void*, int64_t, const void*, int64_t,   \
-                                              X6Args);                                                        \
-  template void launch_g8_f32out<T, 1, 0, X6>(const mmfd_gemm_args&, const EpiArgs&, float*, int, int, float*, \
-                                              int, hipStream_t, const void*, int64_t, const void*, int64_t,   \
-                                              X6Args);                                                        \
-  template void launch_g8_f32out<T, 1, 1, X6>(const mmfd_gemm_args&, const EpiArgs&, float*, int, int, float*, \
-                                              int, hipStream_t, const void*, int64_t, const void*, int64_t,   \
-                                              X6Args);
+#define MMFD_F32OUT_L(T, TA, TB, X6) \
+  template void launch_g8_f32out<T, TA, TB, X6>(const mmfd_gemm_args&, const EpiArgs&, const G8Launch&, hipStream_t);
+#define MMFD_F32OUT(T, X6) \
+  MMFD_F32OUT_L(T, 0, 0, X6) MMFD_F32OUT_L(T, 0, 1, X6) MMFD_F32OUT_L(T, 1, 0, X6) MMFD_F32OUT_L(T, 1, 1, X6)
 MMFD_F32OUT(bf16, false)
 MMFD_F32OUT(bf16, true)
 MMFD_F32OUT(float, false)

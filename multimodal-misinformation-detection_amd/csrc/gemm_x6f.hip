@@ -505,53 +505,26 @@ extern "C" int mmfd_debug_xf_stamps(void* host_dst, int64_t bytes) {
 
 namespace mmfd_gemmx {
 template <int TA, int TB>
-void launch_x6f(const mmfd_gemm_args& a, const EpiArgs& e, float* ws, int splits, int sps, float* rs_out,
-                int rs_mode, hipStream_t s, const void* pa, const void* pb, X6Args x6) {
-  dim3 grid((unsigned)((a.N + G8_BN - 1) / G8_BN), (unsigned)((a.M + G8_BM - 1) / G8_BM), (unsigned)splits);
-  static bool attr = [] {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_x6f_kernel<TA, TB>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS) == hipSuccess &&
-           hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_x6f_act_kernel<TA, TB>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS) == hipSuccess &&
-           hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_x6f_ext_kernel<TA, TB>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS) == hipSuccess;
-  }();
-  (void)attr;
-  // the planes' leading dim = the stored column count
-  const int64_t lda = TA == 0 ? a.K : a.M, ldb = TB == 0 ? a.K : a.N;
-  // (with split-K slabs the tile kernel runs no epilogue at all: the reduce does)
-  const bool lean = ws != nullptr || (e.act == MMFD_ACT_NONE && e.p <= 0.f);
-  const bool ext = !lean && (e.act == MMFD_ACT_GELU_D || e.act == MMFD_ACT_MUL_AUX);  // (no dropout: gemm.hip ext_slab)
-  if (ext)
-    hipLaunchKernelGGL((gemm256_x6f_ext_kernel<TA, TB>), grid, dim3(NT), G8_LDS, s, (const bf16*)pa, lda,
-                       (const bf16*)pb, ldb, (float*)a.C, a.ldc, ws, a.M, a.N, a.K, a.alpha, sps, e, rs_out,
-                       a.a_rowsum_beta, rs_mode, x6);
-  else if (lean)
-    hipLaunchKernelGGL((gemm256_x6f_kernel<TA, TB>), grid, dim3(NT), G8_LDS, s, (const bf16*)pa, lda, (const bf16*)pb,
-                       ldb, (float*)a.C, a.ldc, ws, a.M, a.N, a.K, a.alpha, sps, e, rs_out, a.a_rowsum_beta, rs_mode, x6);
-  else
-    hipLaunchKernelGGL((gemm256_x6f_act_kernel<TA, TB>), grid, dim3(NT), G8_LDS, s, (const bf16*)pa, lda,
-                       (const bf16*)pb, ldb, (float*)a.C, a.ldc, ws, a.M, a.N, a.K, a.alpha, sps, e, rs_out,
-                       a.a_rowsum_beta, rs_mode, x6);
+void launch_x6f(const mmfd_gemm_args& a, const EpiArgs& e, const G8Launch& L, hipStream_t s) {
+#define X6F_GO(KERNEL)                                                                                       \
+  lds_max<&KERNEL<TA, TB>>(G8_LDS);                                                                          \
+  hipLaunchKernelGGL((KERNEL<TA, TB>), L.grid, dim3(NT), G8_LDS, s, (const bf16*)L.A, L.lda, (const bf16*)L.B, \
+                     L.ldb, (float*)a.C, a.ldc, L.ws, a.M, a.N, a.K, a.alpha, L.tps, e, L.rs_out, a.a_rowsum_beta, \
+                     L.rs_mode, L.x6)
+  if (L.form == G8_EXT) { X6F_GO(gemm256_x6f_ext_kernel); }
+  else if (L.form == G8_LEAN) { X6F_GO(gemm256_x6f_kernel); }
+  else { X6F_GO(gemm256_x6f_act_kernel); }
+#undef X6F_GO
 }
-void launch_conv_x6f(const mmfd_gemm_args& a, const EpiArgs& e, float* ws, int splits, int sps, hipStream_t s,
-                     const void* pa, const void* pb, X6Args x6, const ConvGeom& cg) {
-  dim3 grid((unsigned)((a.N + G8_BN - 1) / G8_BN), (unsigned)((a.M + G8_BM - 1) / G8_BM), (unsigned)splits);
-  static bool attr = [] {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_x6f_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS) == hipSuccess;
-  }();
-  (void)attr;
-  hipLaunchKernelGGL(conv_x6f_kernel, grid, dim3(NT), G8_LDS, s, (const bf16*)pa, (const bf16*)pb, a.K, (float*)a.C,
-                     a.ldc, ws, a.M, a.N, a.K, a.alpha, sps, e, x6, cg);
-}
-void dispatch_x6f(const mmfd_gemm_args& a, const EpiArgs& e, float* ws, int splits, int sps, float* rs_out,
-                  int rs_mode, hipStream_t s, const void* pa, const void* pb, X6Args x6, const ConvGeom& cg) {
-  if (cg.on) launch_conv_x6f(a, e, ws, splits, sps, s, pa, pb, x6, cg);
-  else if (!a.trans_a && !a.trans_b) launch_x6f<0, 0>(a, e, ws, splits, sps, rs_out, rs_mode, s, pa, pb, x6);
-  else if (!a.trans_a && a.trans_b) launch_x6f<0, 1>(a, e, ws, splits, sps, rs_out, rs_mode, s, pa, pb, x6);
-  else if (a.trans_a && !a.trans_b) launch_x6f<1, 0>(a, e, ws, splits, sps, rs_out, rs_mode, s, pa, pb, x6);
-  else launch_x6f<1, 1>(a, e, ws, splits, sps, rs_out, rs_mode, s, pa, pb, x6);
+template void launch_x6f<0, 0>(const mmfd_gemm_args&, const EpiArgs&, const G8Launch&, hipStream_t);
+template void launch_x6f<0, 1>(const mmfd_gemm_args&, const EpiArgs&, const G8Launch&, hipStream_t);
+template void launch_x6f<1, 0>(const mmfd_gemm_args&, const EpiArgs&, const G8Launch&, hipStream_t);
+template void launch_x6f<1, 1>(const mmfd_gemm_args&, const EpiArgs&, const G8Launch&, hipStream_t);
+
+void launch_conv_x6f(const mmfd_gemm_args& a, const EpiArgs& e, const G8Launch& L, const ConvGeom& cg, hipStream_t s) {
+  lds_max<&conv_x6f_kernel>(G8_LDS);
+  hipLaunchKernelGGL(conv_x6f_kernel, L.grid, dim3(NT), G8_LDS, s, (const bf16*)L.A, (const bf16*)L.B, L.ldb,
+                     (float*)a.C, a.ldc, L.ws, a.M, a.N, a.K, a.alpha, L.tps, e, L.x6, cg);
 }
 
 }  // namespace mmfd_gemmx

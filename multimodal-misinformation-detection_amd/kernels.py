@@ -421,20 +421,50 @@ def set_g4_persist(on=None):
     return bool(old)
 
 
+_PLAN_BUF = None
+
+
+def _gemm_plan(a, whole_workspace=False):
+    """the launch plan mmfd_gemm makes for `a` with the workspace it carries, or with the one
+    mmfd_gemm_workspace_bytes asks for, as the callers here supply (csrc/gemm.hip
+    mmfd_debug_gemm_plan; host arithmetic only): (path, kernel name as GemmProbe keys it), or
+    (None, None) when the library refuses the call"""
+    global _PLAN_BUF
+    if whole_workspace:
+        a.workspace_bytes = lib().mmfd_gemm_workspace_bytes(ctypes.byref(a))
+        a.workspace = _PLACEHOLDER if a.workspace_bytes > 0 else None
+    fn = lib().mmfd_debug_gemm_plan
+    if _PLAN_BUF is None:
+        fn.restype, fn.argtypes = ctypes.c_int, [ctypes.POINTER(GemmArgs), ctypes.c_char_p, ctypes.c_int64]
+        _PLAN_BUF = ctypes.create_string_buffer(2048)
+    if fn(ctypes.byref(a), _PLAN_BUF, len(_PLAN_BUF)) != 0 or not _PLAN_BUF.value:
+        return None, None
+    head, *launches = _PLAN_BUF.value.decode().splitlines()
+    main = next(l for l in launches if not l.startswith("split3_kernel"))
+    name = main.split(" grid=")[0].split(" tiles=")[0]
+    return head.split(" ")[0][len("path="):], name + (" (split-K)" if " ws=0," in head else "")
+
+
+_PLACEHOLDER = 1 << 20  # a 16-B aligned address for tensors that do not exist yet: a plan never dereferences it
+
+
 def g4_takes(x2d, W, act, residual=None, dropout_p=0.0):
-    """whether the four-wave GEMM runs x2d @ W^T (bf16 nn.Linear forward, contiguous operands) with
-    this epilogue — mirrors mmfd_gemmx::g4_epi's shape / mode conditions; blocks.linear saves the
-    GELU derivative (MMFD_ACT_GELU_D) only for products it takes (elsewhere GELU_D runs through a
-    split-K slab and the reduce, which costs more than the backward's erf it saves)"""
-    mode, kmax = g4_mode()
-    if mode == "off" or x2d.dtype != torch.bfloat16 or W.dtype != torch.bfloat16:
+    """whether the four-wave GEMM runs x2d @ W^T (bf16 nn.Linear forward) with a bias / activation
+    epilogue — asked of the library's launch plan; blocks.linear saves the GELU derivative
+    (MMFD_ACT_GELU_D) only for products it takes (elsewhere GELU_D runs through a split-K slab and
+    the reduce, which costs more than the backward's erf it saves). Epilogues with a residual or
+    dropout never save one: False."""
+    if residual is not None or dropout_p > 0 or x2d.dtype != W.dtype:
         return False
-    if act in (ACT_GELU, ACT_GELU_D) and mode != "gelu":
-        return False
-    (M, Kd), N = x2d.shape, W.shape[0]
-    if M % 256 or N % 256 or Kd % 64 or Kd < 64 or Kd > kmax or residual is not None or dropout_p > 0:
-        return False
-    return _ld(x2d) % 8 == 0 and _ld(W) % 8 == 0 and x2d.data_ptr() % 16 == 0 and W.data_ptr() % 16 == 0
+    a = GemmArgs()
+    a.dtype = a.c_dtype = dtype_code(x2d.dtype)
+    (a.M, a.K), a.N = x2d.shape, W.shape[0]
+    a.A, a.lda, a.B, a.ldb = x2d.data_ptr(), _ld(x2d), W.data_ptr(), _ld(W)
+    a.C, a.ldc, a.alpha = _PLACEHOLDER, a.N, 1.0
+    a.ep.act = int(act)
+    if act in (ACT_GELU_BWD, ACT_RELU_BWD, ACT_GELU_D, ACT_MUL_AUX):
+        a.ep.aux, a.ep.ldaux = _PLACEHOLDER, a.N
+    return _gemm_plan(a, whole_workspace=True)[0] == "g4"
 
 
 def g4_mode():
@@ -449,30 +479,6 @@ def fp32_gemm_mode():
         lib().mmfd_set_fp32_gemm_mode(old)
         _FP32_MODE = old
     return _FP32_MODE
-
-
-def _kernel_name(a, split):
-    """the device kernel mmfd_gemm launches for these arguments (rocprof's demangled name)"""
-    t = {F32: "float", BF16: "__bf16"}
-    narrow = a.M >= 4096 and (a.N <= 128 or a.K < 64)  # gemm.hip use_g8
-    g8 = not narrow and (a.dtype == BF16 or a.c_dtype == F32)
-    if g8:  # 256x256 kernel; PRE = one prefetched bf16 epilogue operand stream; X6 = split operands
-        streams = int(bool(a.ep.residual)) + int(a.ep.act in (ACT_GELU_BWD, ACT_RELU_BWD, ACT_MUL_AUX)) + int(a.beta != 0.0)
-        pre = a.c_dtype == BF16 and streams == 1 and not split
-        x6 = _x6(a)
-        # the lean instantiations (no activation / dropout, or split-K slabs) keep the plain names
-        lean = split or (a.ep.act == ACT_NONE and a.ep.dropout_p <= 0.0)
-        if x6 == 2:  # gemm_x6f.hip launch_x6f (ext: GELU_D / MUL_AUX in the kernel's own epilogue)
-            ext = not lean and a.ep.act in (ACT_GELU_D, ACT_MUL_AUX)
-            base = f"gemm256_x6f{'' if lean else '_ext' if ext else '_act'}_kernel<{a.trans_a}, {a.trans_b}>"
-        else:  # gemm256.h launch_g8_v
-            base = (f"gemm256{'' if lean else '_act'}_kernel<{t[BF16 if x6 else a.dtype]}, {a.trans_a}, {a.trans_b}, "
-                    f"{t[a.c_dtype]}, {'true' if pre else 'false'}, {'true' if x6 else 'false'}>")
-    elif a.N <= 64 and not a.trans_b:  # gemm.hip launch_mfma: the 256x64 tile
-        base = f"gemm_mfma_n64_kernel<{t[a.dtype]}, {a.trans_a}, {t[a.c_dtype]}>"
-    else:
-        base = f"gemm_mfma_kernel<{t[a.dtype]}, {a.trans_a}, {a.trans_b}, {t[a.c_dtype]}>"
-    return base + (" (split-K)" if split else "")
 
 
 def gemm(A, B, *, trans_a=False, trans_b=False, out=None, out_dtype=None, alpha=1.0, beta=0.0, bias=None,
@@ -534,57 +540,30 @@ def gemm(A, B, *, trans_a=False, trans_b=False, out=None, out_dtype=None, alpha=
     return out
 
 
-def _g4_mode(A, B, out, trans_a, trans_b, residual, act, beta, splits, alpha, residual_first, dropout_p, a_rowsum,
-             aux, bias):
-    """the four-wave kernel's epilogue mode for this product, or None (mirrors mmfd_gemmx::launch_g4;
-    GemmProbe bookkeeping only)"""
-    g4, kmax = g4_mode()  # the library's own switches (mmfd_set_g4_mode)
-    if g4 == "off" or trans_a or trans_b or splits > 1 or a_rowsum is not None:
-        return None
-    if A.dtype != torch.bfloat16 or out.dtype != torch.bfloat16 or alpha != 1.0 or beta != 0.0:
-        return None
-    M, K = A.shape
-    N = B.shape[0]
-    if M % 256 or N % 256 or K % 64 or K < 64 or K > kmax:
-        return None
-    ts = [t for t in (A, B, out, residual, aux, bias) if t is not None]
-    if any(t.data_ptr() % 16 for t in ts) or any(_ld(t) % 8 for t in (A, B, out, residual, aux) if t is not None):
-        return None
-    if act == ACT_NONE and residual is None and dropout_p <= 0:
-        return 0
-    if act == ACT_NONE and residual is not None and not residual_first:
-        return 2 if dropout_p > 0 else 1
-    if act == ACT_GELU and residual is None and dropout_p <= 0 and g4 == "gelu":
-        return 3
-    if act == ACT_GELU_BWD and aux is not None and residual is None and dropout_p <= 0:
-        return 4
-    if act == ACT_GELU_D and residual is None and dropout_p <= 0 and g4 == "gelu":
-        return 5
-    if act == ACT_MUL_AUX and aux is not None and residual is None and dropout_p <= 0:
-        return 6
-    return None
-
-
 def _probe_name(A, B, out, trans_a, trans_b, residual, act, beta, splits, alpha=1.0, residual_first=False,
                 dropout_p=0.0, a_rowsum=None, aux=None, bias=None):
-    """the kernel instantiation mmfd_gemm picks (GemmProbe bookkeeping only)"""
-    g4 = _g4_mode(A, B, out, trans_a, trans_b, residual, act, beta, splits, alpha, residual_first, dropout_p,
-                  a_rowsum, aux, bias)
-    if g4 is not None:
-        return f"gemm_g4_kernel<{g4}>"
-    M, K = (A.shape[1], A.shape[0]) if trans_a else A.shape
-    N = B.shape[1] if trans_b else B.shape[0]
+    """the kernel instantiation mmfd_gemm ran for these arguments, read from its launch plan with the
+    workspace the library asks for (GemmProbe bookkeeping only)"""
     a = GemmArgs()
     a.dtype, a.c_dtype = dtype_code(A.dtype), dtype_code(out.dtype)
     a.trans_a, a.trans_b = int(bool(trans_a)), int(bool(trans_b))
-    a.M, a.N, a.K = M, N, K
+    a.M, a.K = (A.shape[1], A.shape[0]) if trans_a else A.shape
+    a.N = B.shape[1] if trans_b else B.shape[0]
     a.A, a.lda, a.B, a.ldb = A.data_ptr(), _ld(A), B.data_ptr(), _ld(B)
     a.C, a.ldc = out.data_ptr(), _ld(out)
-    a.beta, a.splits = float(beta), int(splits)
+    a.alpha, a.beta, a.splits = float(alpha), float(beta), int(splits)
+    a.ep.act, a.ep.residual_first = int(act), int(bool(residual_first))
     if residual is not None:
         a.ep.residual, a.ep.ldr = residual.data_ptr(), _ld(residual)
-    a.ep.act = int(act)
-    return _kernel_name(a, lib().mmfd_gemm_splits(ctypes.byref(a)) > 1)
+    if aux is not None:
+        a.ep.aux, a.ep.ldaux = aux.data_ptr(), _ld(aux)
+    if bias is not None:
+        a.ep.bias = bias.data_ptr()
+    if dropout_p > 0:
+        a.ep.dropout_p, a.ep.seed = float(dropout_p), _PLACEHOLDER
+    if a_rowsum is not None:
+        a.a_rowsum = a_rowsum.data_ptr()
+    return _gemm_plan(a, whole_workspace=True)[1]
 
 
 def split3(x, out=None):
@@ -1213,10 +1192,7 @@ def conv2d_nhwc(x, N, H, W, C, w, k, stride, pad, bias=None, act=ACT_NONE, resid
     if rec:
         e1 = torch.cuda.Event(enable_timing=True)
         e1.record()
-        split = lib().mmfd_gemm_splits(ctypes.byref(a)) > 1
-        tn = "__bf16" if x.dtype == torch.bfloat16 else "float"
-        name = ("conv_x6f_kernel" if _x6(a) == 2 else
-                f"conv_mfma_kernel<{tn}, {tn}, {64 if Cout <= 64 else 128}>") + (" (split-K)" if split else "")
+        name = _gemm_plan(a)[1]
         probe.records.append((name, 2 * M * Cout * K, e0, e1))
     return out, Ho, Wo
 

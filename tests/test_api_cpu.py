@@ -46,6 +46,24 @@ def test_error_reporting_without_gpu_compute():
     assert rc != 0 and b"dtype" in K.lib().mmfd_last_error_string()
 
 
+def test_conv_with_trans_b_is_refused_before_any_launch():
+    """only K-contiguous-B convolution kernels exist: a transposed B would be read as [N][K] past its
+    allocation when N > K, so the call is refused on the host"""
+    import ctypes
+    g = K.ConvGeomArgs(2, 14, 14, 256, 3, 3, 1, 1, 14, 14)
+    a = K.GemmArgs()
+    a.dtype = a.c_dtype = K.BF16
+    a.trans_b, a.M, a.N, a.K = 1, 2 * 14 * 14, 512, 9 * 256
+    a.A, a.B, a.C, a.lda, a.ldb, a.ldc = 1 << 20, 2 << 20, 3 << 20, 256, 512, 512
+    a.conv = ctypes.addressof(g)
+    assert K.lib().mmfd_gemm(a, None) == 1000  # MMFD_ERR_INVALID
+    assert "conv needs trans_b = 0" in K.lib().mmfd_last_error_string().decode()
+    a.trans_b, a.ldb = 0, 9 * 256
+    a.trans_a = 1
+    assert K.lib().mmfd_gemm(a, None) == 1000
+    assert "conv needs trans_a = 0" in K.lib().mmfd_last_error_string().decode()
+
+
 def test_struct_of_another_abi_layout_is_refused():
     """a caller built against another layout of mmfd_gemm_args / mmfd_attn_args
     (e.g. round 3's attention struct, 8 bytes shorter before drop_mask) passes another struct_size

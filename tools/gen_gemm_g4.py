@@ -377,13 +377,10 @@ int g4_epi(const mmfd_gemm_args& a, const EpiArgs& e, int splits) {
   return epi;
 }
 
-bool launch_g4(const mmfd_gemm_args& a, const EpiArgs& e, int splits, hipStream_t s) {
-  const int epi = g4_epi(a, e, splits);
-  if (epi < 0) return false;
-  const int64_t tiles = (a.M / 256) * (a.N / 256);
-  // persistent grid: one workgroup per CU (128 KB of LDS: one fits), each walking its tiles
-  const int64_t grid = g_g4_persist ? std::min<int64_t>(tiles, g4_cus()) : tiles;
-#define G4_LAUNCH(E)                                                                                 \
+// epi: the mode g4_epi returned to the plan; grid: the tiles, or (persistent: one workgroup per CU,
+// 128 KB of LDS: one fits, each walking its tiles) min(tiles, g4_cus()) — gemm.hip run_plan
+void launch_g4(const mmfd_gemm_args& a, const EpiArgs& e, int epi, int64_t grid, hipStream_t s) {
+#define G4_LAUNCH(E)                                                                                \
   hipLaunchKernelGGL(gemm_g4_kernel<E>, dim3((unsigned)grid), dim3(256), 0, s, (const bf16*)a.A, a.lda, \
                      (const bf16*)a.B, a.ldb, (bf16*)a.C, a.ldc, e, (int)a.M, (int)a.N, (int)a.K)
   if (epi == 0) G4_LAUNCH(0);
@@ -394,7 +391,6 @@ bool launch_g4(const mmfd_gemm_args& a, const EpiArgs& e, int splits, hipStream_
   else if (epi == 5) G4_LAUNCH(5);
   else G4_LAUNCH(6);
 #undef G4_LAUNCH
-  return true;
 }
 }  // namespace mmfd_gemmx
 
