@@ -575,6 +575,36 @@ int mmfd_beam_reorder(int64_t layers, int64_t rows, int64_t beam_rows, int64_t r
                       const void* const* src, void* const* dst, const int32_t* parent, mmfd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------- */
+/* Vocabulary cross-entropy (csrc/lm_loss.hip): the caption loss of the BLIP text decoder,      */
+/* transformers' BlipTextLMHeadModel with labels = CrossEntropyLoss(label_smoothing = eps,       */
+/* ignore_index = -100) over logits[:, :-1] / labels[:, 1:]. logits: fp32 [R][ldl], V columns    */
+/* used, 16-byte aligned (16-byte loads when ldl % 4 == 0, any V: a scalar tail); labels int64   */
+/* [R]: a label outside [0, V) marks an ignored row (-100 by convention; the Python wrapper      */
+/* refuses any other such value on the host). One workgroup per row, the row maximum taken       */
+/* before the exponentials; every reduction in a fixed order (same inputs, same bits).          */
+/* fwd: loss_rows[r] = lse_r - (1 - eps) z_r[y_r] - (eps / V) sum_v z_r[v] (0 for an ignored     */
+/*   row), lse[r] = log sum_v exp z_r[v] (fp32, what bwd reads) and, optional, lse_lo[r] = the   */
+/*   part of it that fp32 rounded away (lse + lse_lo is the sum to double precision: with it     */
+/*   bwd forms z - lse without the ulp of an lse near 10, which would otherwise sit in the       */
+/*   exponent of the row's largest probabilities); then, each optional (NULL):                   */
+/*   *mean = sum_r loss_rows[r] / valid rows (NaN without a valid row, as torch), *n_valid,      */
+/*   seq_sums[b] = sum of rows b*rows_per_seq .. + rows_per_seq - 1 (rows_per_seq divides R).    */
+/*   Reads R*V*4 bytes.                                                                          */
+/* bwd: dlogits[r][v] (out_dtype, [R][ldd], 16-byte aligned; 16-byte stores when ldl % 4 == 0    */
+/*   and ldd * esz % 16 == 0) = g_r (exp(z - lse_r) - (1 - eps) [v == y_r] - eps / V), lse_r =   */
+/*   lse[r] + lse_lo[r] (lse_lo NULL = 0); g_r = 0                                               */
+/*   (the row is written as exact zeros) for an ignored row, else in the mean form (n_valid      */
+/*   given: fwd's device counter) upstream[0] / *n_valid (upstream NULL = 1), and in the         */
+/*   per-sequence form (n_valid NULL) upstream[r / rows_per_seq]. Moves R*V*(4 + esz) bytes.    */
+/* ------------------------------------------------------------------------------------------- */
+int mmfd_vocab_xent_fwd(int64_t R, int64_t V, const float* logits, int64_t ldl, const int64_t* labels, float eps,
+                        int64_t rows_per_seq, float* loss_rows, float* lse, float* lse_lo, float* mean,
+                        int64_t* n_valid, float* seq_sums, mmfd_stream_t stream);
+int mmfd_vocab_xent_bwd(int out_dtype, int64_t R, int64_t V, const float* logits, int64_t ldl, const int64_t* labels,
+                        const float* lse, const float* lse_lo, float eps, const float* upstream,
+                        const int64_t* n_valid, int64_t rows_per_seq, void* dlogits, int64_t ldd, mmfd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------- */
 /* AdamW (torch.optim.AdamW defaults as used at train.py:356/188), multi-tensor, one launch.    */
 /* table: device array of n_tensors records {param f32*, grad f32*, exp_avg f32*, exp_avg_sq     */
 /* f32*, param_bf16 bf16* (optional shadow copy, may be NULL), step f32*, numel};             */

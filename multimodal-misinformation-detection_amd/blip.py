@@ -1,6 +1,8 @@
 """BLIP image captioning on HIP kernels: the reference's captioning stage (src/preprocess/caption.py:22-31
 and src/demo/app.py run `BlipForConditionalGeneration.from_pretrained("Salesforce/blip-image-captioning-
-large").generate(**inputs)` over every claim and evidence image). Inference only.
+large").generate(**inputs)` over every claim and evidence image), and the caption loss of transformers'
+`forward(..., labels=)`: scoring on any model, fine-tuning of the text decoder with
+`BlipConfig(train_text_decoder=True)` (the vision tower stays frozen; the last item below).
 
 `BlipForConditionalGeneration` keeps transformers' parameter names, so its `state_dict` loads with
 `strict=True`; `generate` follows transformers' greedy default (20 new tokens, decoding from [bos], stop
@@ -25,6 +27,14 @@ What runs where:
     early-stop heuristic, the next token and the parent row of every beam) and kernels.beam_reorder gathers the
     self-attention caches by parent into a second set of buffers: still no host decision between steps and one
     captured graph per (batch, steps, precision, num_beams, length_penalty, early_stopping).
+  * the caption loss (forward(labels=)) shares no code with generation: ONE pass of the decoder over all T
+    positions with no K|V cache — embeddings, per layer the packed Q|K|V GEMM, attn_fwd under a causal additive
+    bias [H, T, T] and the key-padding bias, output projection + LayerNorm, cross-attention of the text rows over
+    the image's K|V, FFN + LayerNorm, then the head transform — the fp32 logits of all B * T rows from one GEMM
+    against the tied embedding table, and kernels.vocab_xent_fwd (csrc/lm_loss.hip). Under grad with
+    train_text_decoder the whole pass is one autograd node (_BlipLossFn) with a hand-written backward that fills
+    the gradient of every text_decoder parameter; vision_model parameters receive None, so the optimizer is
+    handed `model.text_decoder.parameters()` only. Eager; right-padded batches only.
 """
 from __future__ import annotations
 
@@ -63,8 +73,9 @@ class BlipTextConfig:
     eos_token_id: int = 102
     pad_token_id: int = 0
     encoder_hidden_size: int | None = None  # width of the image tokens (default: the vision width)
-    hidden_dropout_prob: float = 0.0        # inference only: accepted and unused
+    hidden_dropout_prob: float = 0.0        # generation: accepted and unused; the loss path refuses > 0 in training mode
     attention_probs_dropout_prob: float = 0.0
+    label_smoothing: float = 0.0            # of the caption loss (transformers' BlipTextConfig.label_smoothing)
 
 
 @dataclass
@@ -72,6 +83,7 @@ class BlipConfig:
     """defaults: Salesforce/blip-image-captioning-large"""
     vision: BlipVisionConfig = field(default_factory=BlipVisionConfig)
     text: BlipTextConfig = field(default_factory=BlipTextConfig)
+    train_text_decoder: bool = False  # forward(labels=) under grad fills the text_decoder gradients (else: refused)
 
     def __post_init__(self):
         if isinstance(self.vision, dict):
@@ -87,6 +99,38 @@ T = "text_decoder.bert."
 HEAD = "text_decoder.cls.predictions."
 WORD = T + "embeddings.word_embeddings"
 PATCH_W = V + "embeddings.patch_embedding.weight"
+QKV = (".attention.self.query", ".attention.self.key", ".attention.self.value")
+CROSS_KV = (".crossattention.self.key", ".crossattention.self.value")
+# The causal mask value. It is added to the key-padding bias of kernels.mask_to_bias (the most negative fp32,
+# -3.4028e38, on a padded key) and to a scaled score: -1e30 is below any score by more than exp() can resolve
+# (exp(-1e30 - m) == 0 exactly), and -3.4028e38 - 1e30 rounds back to -3.4028e38 (1e30 is under half an ulp
+# there), so mask + padding bias stays finite: the softmax never sees -inf, and never forms inf - inf.
+CAUSAL_NEG = -1.0e30
+
+
+def vocab_ld(V):
+    """columns of the logits and dlogits buffers, and rows of the tied table as the LM-head backward reads it: V
+    rounded up to a multiple of 8. Rows of V bf16 or fp32 elements then start 16 bytes aligned, which the vector
+    paths of csrc/lm_loss.hip and the MFMA kernels of mmfd_gemm need of a contiguous extent (BLIP's 30,524 is
+    4 * 7631: unpadded, the two bf16 LM-head backward products fall to the one-output-per-thread kernel)"""
+    return -(-V // 8) * 8
+
+
+def lm_head_gemm_paths(dtype, R, V, E):
+    """the launch plans (kernels.gemm_path: host arithmetic only) of the three LM-head products of the caption loss
+    as _loss_forward and _loss_backward issue them for R rows: the logits, dG = dlogits W, dW = dlogits^T G"""
+    Vp = vocab_ld(V)
+    return {"logits": K.gemm_path(dtype, R, V, E, ldc=Vp, out_dtype=torch.float32, bias=True),
+            "dG": K.gemm_path(dtype, R, E, Vp, trans_b=True),
+            "dW": K.gemm_path(dtype, Vp, E, R, trans_a=True, trans_b=True, out_dtype=torch.float32, a_rowsum=True)}
+
+
+@dataclass
+class BlipCaptionLossOutput:
+    """forward(labels=): `loss` fp32, a scalar (reduction="mean") or the per-sequence sums [B] ("none");
+    `logits` fp32 [B, T, V] when asked for, else None"""
+    loss: torch.Tensor
+    logits: torch.Tensor | None = None
 
 
 def _attn_block(D, kv_in, eps):
@@ -162,6 +206,7 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
         pr.decoder.bias = pr.bias
         self.compute_dtype = torch.float32
         self._states = {}
+        self._causal = {}
         self._init_weights()
 
     def _init_weights(self, std=0.02):
@@ -185,13 +230,14 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
         return super().invalidate_caches()
 
     # ---- plumbing ----------------------------------------------------------------------------------
-    def _ctx(self):
-        """(StepCtx, device) of one call; refuses a CPU model and a call that would need gradients"""
+    def _ctx(self, train=False):
+        """(StepCtx, device) of one call; refuses a CPU model and a call that would need gradients (`train`: the
+        context of _BlipLossFn, whose weight-derived tensors are rebuilt on every call)"""
         params = dict(self.named_parameters())
         dev = next(iter(params.values())).device
         if dev.type != "cuda":
             raise RuntimeError("mmfd BlipForConditionalGeneration runs on the HIP device: call .to('cuda') first")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params.values()):
+        if not train and torch.is_grad_enabled() and any(p.requires_grad for p in params.values()):
             raise NotImplementedError("mmfd BlipForConditionalGeneration is inference-only (the reference only "
                                       "captions with it, caption.py:22-31): call it under torch.no_grad() or "
                                       "freeze its parameters")
@@ -200,7 +246,7 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
         P[HEAD + "decoder.weight"], P[HEAD + "decoder.bias"] = P[WORD + ".weight"], P[HEAD + "bias"]
         P[PATCH_W] = P[PATCH_W].reshape(P[PATCH_W].shape[0], -1)  # conv P/s P == GEMM over patches
         sc = Bk.StepCtx(P, self.compute_dtype, shadows=Bk.shadow_store(self))
-        sc.cache_derived = True
+        sc.cache_derived = not train
         return sc, dev
 
     @staticmethod
@@ -607,6 +653,275 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
         self._ctx()  # (refuses a call that would need gradients before no_grad hides it)
         return self._forward_logits(pixel_values, forced_ids)
 
-    def forward(self, pixel_values, input_ids):
-        """teacher-forced logits [T, B, V] (forward_logits); inference only"""
-        return self.forward_logits(pixel_values, input_ids)
+    def forward(self, pixel_values, input_ids, attention_mask=None, labels=None, reduction="mean", return_logits=False):
+        """Without `labels`: teacher-forced logits [T, B, V] (forward_logits); inference only.
+        With `labels` (int64 [B, T], -100 = not scored): transformers' caption loss, CrossEntropy(logits[:, :-1],
+        labels[:, 1:]) with config.text.label_smoothing, as a BlipCaptionLossOutput — `loss` the mean over the scored
+        positions, or with reduction="none" the per-sequence sums [B]; `logits` [B, T, V] with return_logits.
+        `attention_mask` [B, T] marks right padding (a row starting with padding, or with a token after padding, is
+        refused). Under no_grad this works on any model. Under grad it needs BlipConfig.train_text_decoder: the loss
+        is then one autograd node whose backward fills the gradient of every text_decoder parameter; the vision
+        tower is frozen (its parameters receive None: hand the optimizer model.text_decoder.parameters())."""
+        if labels is None:
+            if attention_mask is not None or return_logits:
+                raise ValueError("attention_mask / return_logits belong to the loss path: pass labels")
+            return self.forward_logits(pixel_values, input_ids)
+        return self._caption_loss(pixel_values, input_ids, attention_mask, labels, reduction, return_logits)
+
+    # ---- caption loss: one pass over all positions -------------------------------------------------------
+    def _causal_bias(self, T_, dev):
+        """the shared additive bias [H, T, T] of the causal mask: 0 on and below the diagonal, CAUSAL_NEG above;
+        built once per (T, device)"""
+        H = self.config.text.num_attention_heads
+        key = (H, T_, str(dev))
+        b = self._causal.get(key)
+        if b is None:
+            if len(self._causal) >= 8:
+                self._causal.clear()
+            m = torch.triu(torch.full((T_, T_), CAUSAL_NEG, dtype=torch.float32, device=dev), diagonal=1)
+            b = self._causal[key] = m[None].expand(H, T_, T_).contiguous()
+        return b
+
+    def _loss_inputs(self, input_ids, attention_mask, labels, dev):
+        """host-side checks, then the device inputs of the pass: ids, positions, mask (or None) [Bp, T] and the
+        shifted labels [Bp * T] (row b * T + t scores token t + 1; the last position of a row, the padding and the
+        rows >= B are -100). Bp > B only when B * T < 16: mmfd_gemm runs fewer than 16 rows on its scalar path"""
+        tc = self.config.text
+        ids = torch.as_tensor(input_ids).long()
+        lab = torch.as_tensor(labels).long()
+        if ids.dim() != 2 or tuple(lab.shape) != tuple(ids.shape):
+            raise ValueError(f"input_ids and labels must be [B, T], got {tuple(ids.shape)} and {tuple(lab.shape)}")
+        B, T_ = ids.shape
+        if not 2 <= T_ <= tc.max_position_embeddings:
+            raise ValueError(f"the sequence length must lie in [2, {tc.max_position_embeddings}], got {T_}")
+        ids_h = ids.cpu()
+        if int(ids_h.min()) < 0 or int(ids_h.max()) >= tc.vocab_size:
+            raise ValueError(f"input_ids outside [0, {tc.vocab_size})")
+        K.check_vocab_labels(lab, tc.vocab_size)
+        mask = None
+        if attention_mask is not None:
+            mask = (torch.as_tensor(attention_mask).cpu() != 0).long()
+            if tuple(mask.shape) != (B, T_):
+                raise ValueError(f"attention_mask must be {(B, T_)}, got {tuple(mask.shape)}")
+            if bool((mask[:, 0] == 0).any()):
+                raise ValueError("a row starts with padding: only right-padded batches are supported")
+            if bool((mask[:, 1:] > mask[:, :-1]).any()):
+                raise ValueError("a token follows padding: only right-padded batches are supported")
+            # what lies under the padding is never attended by a scored position: it is replaced by pad_token_id, so
+            # that no bit of the result depends on it (the embedding backward's summation order follows the sorted
+            # ids, padding included)
+            ids_h = torch.where(mask == 1, ids_h, torch.full_like(ids_h, tc.pad_token_id))
+            if bool(mask.all()):
+                mask = None
+        Bp = B if B * T_ >= 16 else -(-16 // T_)
+        ids_p = torch.zeros(Bp, T_, dtype=torch.int64)
+        ids_p[:B] = ids_h
+        lab_p = torch.full((Bp, T_), K.IGNORE_INDEX, dtype=torch.int64)
+        lab_p[:B, :-1] = lab.cpu()[:, 1:]
+        if mask is not None:
+            mask_p = torch.ones(Bp, T_, dtype=torch.int64)
+            mask_p[:B] = mask
+            mask = mask_p.to(dev)
+        pos = torch.arange(T_, dtype=torch.int64)[None].expand(Bp, T_).contiguous()
+        return ids_p.to(dev), pos.to(dev), mask, lab_p.view(-1).to(dev)
+
+    def _decoder_pass(self, sc, emb, ids, pos, mask, keep):
+        """the decoder over all positions at once: (the LM head's input [Bp * T, E], what the backward reads or
+        None). emb: the image tokens [Bp, Li, Dv]"""
+        tc = self.config.text
+        Bp, T_ = ids.shape
+        E, H, eps, P = tc.hidden_size, tc.num_attention_heads, tc.layer_norm_eps, sc.P
+        emb_args = (ids, pos, P[WORD + ".weight"], P[T + "embeddings.position_embeddings.weight"],
+                    P[T + "embeddings.LayerNorm.weight"], P[T + "embeddings.LayerNorm.bias"], eps, sc.dt)
+        if keep:
+            s0, x, m0, r0 = K.embed_ln_train(*emb_args)
+        else:
+            x, s0, m0, r0 = K.embed_ln_infer(*emb_args), None, None, None
+        kb = K.mask_to_bias(mask) if mask is not None else None
+        causal = self._causal_bias(T_, ids.device)
+        emb2d = Bk.as2d(emb)
+        cross = self._cross_kv(sc, emb)  # per layer the image's packed K|V [Bp, Li, 2E]
+        layers = []
+        for i in range(tc.num_hidden_layers):
+            p = f"{T}encoder.layer.{i}"
+            o, _, attn = Bk.self_attn_fwd(sc, x, [p + n for n in QKV], Bp, H, keep=keep, planes=False, key_bias=kb,
+                                          rel_bias=causal)
+            s1, _ = Bk.linear(sc, Bk.as2d(o), p + ".attention.output.dense", residual=x)
+            h, m1, r1 = Bk.layernorm(sc, s1, p + ".attention.output.LayerNorm", eps)
+            cq, _ = Bk.linear(sc, h, p + ".crossattention.self.query")
+            ckv = cross[i]
+            cq = cq.view(Bp, T_, E)
+            co, clse = K.attn_fwd(cq, ckv[..., :E], ckv[..., E:], H)  # every image key takes part
+            s2, _ = Bk.linear(sc, Bk.as2d(co), p + ".crossattention.output.dense", residual=h)
+            h2, m2, r2 = Bk.layernorm(sc, s2, p + ".crossattention.output.LayerNorm", eps)
+            s3, ffn = Bk.ffn_fwd(sc, h2, p + ".intermediate.dense", p + ".output.dense", residual=h2, keep=keep,
+                                 planes=False)
+            x, m3, r3 = Bk.layernorm(sc, s3, p + ".output.LayerNorm", eps)
+            if keep:
+                layers.append(dict(attn=attn, o=o, s1=s1, m1=m1, r1=r1, h=h, cq=cq, ckv=ckv, co=co, clse=clse, s2=s2,
+                                   m2=m2, r2=r2, ffn=ffn, s3=s3, m3=m3, r3=r3))
+        # the head transform: dense + GELU (the pre-activation kept for the backward), then LayerNorm
+        W = sc.w(HEAD + "transform.dense")
+        pre = torch.empty((x.shape[0], E), device=x.device, dtype=sc.dt) if keep else None
+        g = K.gemm(x, W, bias=sc.b(HEAD + "transform.dense"), act=K.ACT_GELU, aux=pre)
+        gl, mg, rg = Bk.layernorm(sc, g, HEAD + "transform.LayerNorm", eps)
+        st = dict(s0=s0, m0=m0, r0=r0, layers=layers, x=x, pre=pre, g=g, mg=mg, rg=rg, gl=gl, emb2d=emb2d, ids=ids,
+                  Bp=Bp, T=T_) if keep else None
+        return gl, st
+
+    def _loss_forward(self, sc, dev, pixel_values, input_ids, attention_mask, labels, keep, eps):
+        """the vision tower (never kept: frozen), the decoder pass, the logits of all Bp * T rows and the loss
+        kernels with label smoothing eps: a dict of device tensors and, with `keep`, the backward's state"""
+        tc = self.config.text
+        ids, pos, mask, lab = self._loss_inputs(input_ids, attention_mask, labels, dev)
+        Bp, T_ = ids.shape
+        B = int(torch.as_tensor(input_ids).shape[0])
+        px = pixel_values.to(dev).float().contiguous()
+        if px.shape[0] != B:
+            raise ValueError(f"pixel_values holds {px.shape[0]} images, input_ids {B} rows")
+        emb = self._vision(sc, px)
+        if Bp > B:
+            pad = torch.zeros((Bp,) + tuple(emb.shape[1:]), device=dev, dtype=emb.dtype)
+            pad[:B] = emb
+            emb = pad
+        gl, st = self._decoder_pass(sc, emb, ids, pos, mask, keep)
+        V = tc.vocab_size
+        logits = torch.empty((gl.shape[0], vocab_ld(V)), device=dev, dtype=torch.float32)[:, :V]  # [Bp * T, V]
+        K.gemm(gl, sc.w(WORD), bias=sc.P[HEAD + "bias"], out=logits)
+        rows, lse, lse_lo, mean, n_valid, seq = K.vocab_xent_fwd(logits, lab, eps, rows_per_seq=T_,
+                                                                 check_labels=False)
+        out = dict(B=B, T=T_, eps=eps, logits=logits, labels=lab, lse=lse, lse_lo=lse_lo, mean=mean, n_valid=n_valid,
+                   seq=seq)
+        return out, st
+
+    def _loss_backward(self, sc, out, st, reduction, dout):
+        """fills sc.grads with the gradient of every text_decoder parameter (fp32), in a fixed order"""
+        tc = self.config.text
+        E, H, eps = tc.hidden_size, tc.num_attention_heads, tc.layer_norm_eps
+        Bp, T_, B = st["Bp"], st["T"], out["B"]
+        dev = out["logits"].device
+        V = tc.vocab_size
+        Vp = vocab_ld(V)
+        # 1. dlogits in the compute dtype, in vocab_ld(V) columns: the vocabulary is the K of one LM-head product and
+        #    the M of the other, and the columns past V are zeros, so they add nothing to either
+        dl = torch.empty((Bp * T_, Vp), device=dev, dtype=sc.dt)
+        if Vp > V:
+            dl[:, V:].zero_()
+        xent = (out["logits"], out["labels"], out["lse"], out["lse_lo"], out["eps"], sc.dt)
+        if reduction == "mean":
+            K.vocab_xent_bwd(*xent, upstream=dout.reshape(1).float().contiguous(), n_valid=out["n_valid"], out=dl[:, :V])
+        else:
+            up = torch.zeros(Bp, device=dev, dtype=torch.float32)
+            up[:B] = dout.float()
+            K.vocab_xent_bwd(*xent, upstream=up, rows_per_seq=T_, out=dl[:, :V])
+        # 2. the LM head: dG = dlogits W; dW = dlogits^T G and d(bias) = column sums, into the fp32 gradient of the
+        #    tied table (the embedding scatter is added to it at the end: one fixed order). With Vp > V the table is
+        #    copied into Vp rows, the last ones zero, and the gradients are the first V rows of Vp-row buffers
+        Wv = sc.w(WORD)
+        if Vp > V:
+            Wv = torch.empty((Vp, E), device=dev, dtype=sc.dt)
+            K.cast(sc.P[WORD + ".weight"], sc.dt, out=Wv[:V])
+            Wv[V:].zero_()
+        gword = torch.empty((Vp, E), device=dev, dtype=torch.float32)
+        gbias = torch.empty(Vp, device=dev, dtype=torch.float32)
+        K.gemm(dl, st["gl"], trans_a=True, trans_b=True, out=gword, a_rowsum=gbias)
+        gword, gbias = gword[:V], gbias[:V]
+        sc.grads[WORD + ".weight"], sc.grads[HEAD + "bias"] = gword, gbias
+        dgl = Bk.linear_dx(sc, dl, Wv)
+        del dl, Wv
+        # 3. the head transform
+        dg, _ = Bk.layernorm_bwd(sc, dgl, st["g"], HEAD + "transform.LayerNorm", st["mg"], st["rg"])
+        dpre = K.act_bwd(dg, st["pre"], K.ACT_GELU)
+        sc.lin_grads([HEAD + "transform.dense"], dpre, st["x"])
+        dx = Bk.linear_dx(sc, dpre, HEAD + "transform.dense")
+        # 4. the layers in reverse
+        for i in reversed(range(tc.num_hidden_layers)):
+            p = f"{T}encoder.layer.{i}"
+            ls = st["layers"][i]
+            ds3, _ = Bk.layernorm_bwd(sc, dx, ls["s3"], p + ".output.LayerNorm", ls["m3"], ls["r3"])
+            dh2 = Bk.ffn_bwd(sc, ds3, None, ls["ffn"], residual=ds3)
+            ds2, _ = Bk.layernorm_bwd(sc, dh2, ls["s2"], p + ".crossattention.output.LayerNorm", ls["m2"], ls["r2"])
+            dco = Bk.attn_out_bwd(sc, p + ".crossattention.output.dense", ds2, None, ls["co"], None)
+            ckv = ls["ckv"]
+            dkv = torch.empty_like(ckv)
+            dcq, _, _ = K.attn_bwd(ls["cq"], ckv[..., :E], ckv[..., E:], ls["co"], ls["clse"], dco, H,
+                                   dk=dkv[..., :E], dv=dkv[..., E:])
+            # dK|dV reach the key / value projections, whose input is the saved image tokens; no gradient is
+            # formed for the image tokens themselves (the vision tower is frozen)
+            sc.lin_grads([p + n for n in CROSS_KV], Bk.as2d(dkv), st["emb2d"])
+            sc.lin_grads([p + ".crossattention.self.query"], Bk.as2d(dcq), ls["h"])
+            dh = Bk.linear_dx(sc, Bk.as2d(dcq), p + ".crossattention.self.query", residual=ds2)
+            ds1, _ = Bk.layernorm_bwd(sc, dh, ls["s1"], p + ".attention.output.LayerNorm", ls["m1"], ls["r1"])
+            do = Bk.attn_out_bwd(sc, p + ".attention.output.dense", ds1, None, ls["o"], None)
+            dx = Bk.self_attn_bwd(sc, do, ls["attn"], residual=ds1)
+        # 5. the embedding LayerNorm, then the scatter into the word table (on top of the LM-head term) and the
+        #    position table
+        dsum, _ = Bk.layernorm_bwd(sc, dx, st["s0"], T + "embeddings.LayerNorm", st["m0"], st["r0"])
+        pname = T + "embeddings.position_embeddings.weight"
+        dpos = K.zeros(sc.P[pname].shape, device=dev)
+        K.embed_bwd(st["ids"], None, dsum, gword, dpos, None, padding_idx=tc.pad_token_id)
+        sc.grads[pname] = dpos
+
+    def _caption_loss(self, pixel_values, input_ids, attention_mask, labels, reduction, return_logits,
+                      label_smoothing=None):
+        """forward(labels=); label_smoothing: a value to use in place of config.text.label_smoothing
+        (Captioner.score: 0)"""
+        tc = self.config.text
+        eps = float(tc.label_smoothing if label_smoothing is None else label_smoothing)
+        if reduction not in ("mean", "none"):
+            raise ValueError(f"reduction must be 'mean' or 'none', got {reduction!r}")
+        if self.training and (tc.hidden_dropout_prob > 0 or tc.attention_probs_dropout_prob > 0):
+            raise NotImplementedError("mmfd BLIP's caption loss supports the BLIP text configuration (dropout 0): "
+                                      "call .eval() or set the text dropout probabilities to 0")
+        named = [(n, p) for n, p in self.named_parameters() if n.startswith("text_decoder.")]
+        grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if grad and not self.config.train_text_decoder:
+            self._ctx()  # raises the inference-only error
+        if grad:
+            loss, logits = _BlipLossFn.apply(self, [n for n, _ in named], pixel_values, input_ids, attention_mask, labels,
+                                             reduction, bool(return_logits), eps, *[p for _, p in named])
+            return BlipCaptionLossOutput(loss=loss, logits=logits if return_logits else None)
+        with torch.no_grad():
+            sc, dev = self._ctx()
+            out, _ = self._loss_forward(sc, dev, pixel_values, input_ids, attention_mask, labels, False, eps)
+        return BlipCaptionLossOutput(loss=self._pick_loss(out, reduction), logits=self._pick_logits(out, return_logits))
+
+    @staticmethod
+    def _pick_loss(out, reduction):
+        return out["mean"] if reduction == "mean" else out["seq"][:out["B"]]
+
+    @staticmethod
+    def _pick_logits(out, return_logits):
+        if not return_logits:
+            return None
+        B, T_ = out["B"], out["T"]
+        return out["logits"][:B * T_].contiguous().view(B, T_, -1)  # (a copy only where vocab_ld(V) > V)
+
+
+class _BlipLossFn(torch.autograd.Function):
+    """the caption loss of a model with train_text_decoder as one autograd node over the text_decoder parameters"""
+
+    @staticmethod
+    def forward(fctx, model, names, pixel_values, input_ids, attention_mask, labels, reduction, return_logits, eps,
+                *params):
+        sc, dev = model._ctx(train=True)
+        out, st = model._loss_forward(sc, dev, pixel_values, input_ids, attention_mask, labels, True, eps)
+        fctx.sc, fctx.st, fctx.out, fctx.model, fctx.names, fctx.reduction = sc, st, out, model, names, reduction
+        loss = model._pick_loss(out, reduction).clone()
+        logits = model._pick_logits(out, return_logits)
+        if logits is None:
+            logits = loss.new_empty(0)
+        fctx.mark_non_differentiable(logits)
+        return loss, logits
+
+    @staticmethod
+    def backward(fctx, dloss, _dlogits):
+        sc = fctx.sc
+        if sc is None:
+            raise RuntimeError("mmfd BLIP: the caption loss was already backpropagated (its saved state is dropped)")
+        sc.enable_side_stream(dloss.device)
+        fctx.model._loss_backward(sc, fctx.out, fctx.st, fctx.reduction, dloss)
+        sc.join_side()
+        grads = [sc.grads.get(n) for n in fctx.names]
+        fctx.sc = fctx.st = fctx.out = None
+        return (None,) * 9 + tuple(grads)

@@ -5,8 +5,9 @@ processor.decode(out[0], skip_special_tokens=True)`) and the same call in src/de
 `Captioner` takes what the reference's processor takes — a PIL image, or a list of PIL images / uint8 HWC
 arrays, resized and normalised on the device by mmfd.preprocess.ImagePreprocessor("blip") bit for bit as
 transformers' BlipImageProcessor does it — or already preprocessed pixel tensors ([B, 3, S, S]). Decoding is
-greedy or, with num_beams > 1, transformers' beam search (mmfd.blip, csrc/beam.hip). Still to follow: the
-resumable CSV driver, sampling, and training."""
+greedy or, with num_beams > 1, transformers' beam search (mmfd.blip, csrc/beam.hip). `Captioner.score` gives the
+log-likelihood of given captions (the model's forward(labels=), csrc/lm_loss.hip): perplexity on held-out captions,
+re-scoring of hypotheses. Still to follow: the resumable CSV driver and sampling."""
 from __future__ import annotations
 
 import torch
@@ -65,3 +66,26 @@ class Captioner:
         else:
             out = [self.tokenizer.decode(r, skip_special_tokens=True) for r in ids.tolist()]
         return [s.strip() for s in out]
+
+    @torch.no_grad()
+    def score(self, pixel_values, captions):
+        """(log-likelihoods fp32 [B], token counts int64 [B]): for every (image, caption) pair the summed
+        log-probability of the caption's tokens after the first — the negated reduction="none" caption loss without
+        label smoothing — and the number of tokens summed. The captions are tokenised with the captioner's tokenizer
+        and padded on the right; the first token becomes bos_token_id, as in `generate`; padding is not scored."""
+        if self.tokenizer is None:
+            raise ValueError("Captioner.score needs a tokenizer (Captioner(model, tokenizer=...))")
+        px = self.pixels(pixel_values)
+        if isinstance(captions, str):
+            captions = [captions]
+        if self.tokenizer.padding_side != "right":
+            raise ValueError("Captioner.score needs a tokenizer that pads on the right")
+        enc = self.tokenizer(list(captions), padding=True, return_tensors="pt")
+        ids, mask = enc["input_ids"].long().clone(), enc["attention_mask"].long()
+        if ids.shape[0] != px.shape[0]:
+            raise ValueError(f"{px.shape[0]} images but {ids.shape[0]} captions")
+        tc = self.model.config.text
+        ids[:, 0] = tc.bos_token_id
+        labels = ids.masked_fill(mask == 0, -100)
+        out = self.model._caption_loss(px, ids, mask, labels, "none", False, label_smoothing=0.0)
+        return -out.loss, (labels[:, 1:] != -100).sum(1)

@@ -221,6 +221,8 @@ SIGNATURES = {
     "mmfd_beam_select": (_I, [_I64, _I64, _I64, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
     "mmfd_beam_update": (_I, [_I64, _I64, _I64, _I64, _I64, _I, _I, _I64, _F] + [_VP] * 12 + [_I64, _VP]),
     "mmfd_beam_reorder": (_I, [_I64, _I64, _I64, _I64, _I64, _VP, _VP, _VP, _VP]),
+    "mmfd_vocab_xent_fwd": (_I, [_I64, _I64, _VP, _I64, _VP, _F, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mmfd_vocab_xent_bwd": (_I, [_I, _I64, _I64, _VP, _I64, _VP, _VP, _VP, _F, _VP, _VP, _I64, _VP, _I64, _VP]),
 }
 
 _lib = None
@@ -593,6 +595,26 @@ def x6_ok(M, N, K, trans_a=False, trans_b=False):
     a.ldb = N if trans_b else K
     a.ldc = N
     return lib().mmfd_gemm_runs_split(ctypes.byref(a)) != 0
+
+
+def gemm_path(dtype, M, N, K, *, trans_a=False, trans_b=False, lda=None, ldb=None, ldc=None, out_dtype=None,
+              bias=False, a_rowsum=False):
+    """(path, kernel) of mmfd_gemm's launch plan for a product of these shapes and leading dimensions (default:
+    contiguous operands) on 16-B aligned operands, with the workspace the library asks for — host arithmetic
+    only, as x6_ok; path "simple" is the one-output-per-thread FMA kernel"""
+    a = GemmArgs()
+    a.dtype, a.c_dtype = dtype_code(dtype), dtype_code(out_dtype or dtype)
+    a.trans_a, a.trans_b = int(bool(trans_a)), int(bool(trans_b))
+    a.M, a.N, a.K = int(M), int(N), int(K)
+    a.A = a.B = a.C = _PLACEHOLDER
+    a.lda = int(lda or (M if trans_a else K))
+    a.ldb = int(ldb or (N if trans_b else K))
+    a.ldc, a.alpha = int(ldc or N), 1.0
+    if bias:
+        a.ep.bias = _PLACEHOLDER
+    if a_rowsum:
+        a.a_rowsum = _PLACEHOLDER
+    return _gemm_plan(a, whole_workspace=True)
 
 
 def split_eligible(x):
@@ -1636,3 +1658,78 @@ def beam_reorder(src, dst, src_table, dst_table, parent, beam_rows, n_pos):
     es = a.element_size()
     _check(lib().mmfd_beam_reorder(len(src), rows, int(beam_rows), steps * width * es, int(n_pos) * width * es,
                                    _ptr(src_table), _ptr(dst_table), _ptr(parent), _stream()), "mmfd_beam_reorder")
+
+
+# ------------------------------------------------------------------------------------------------
+# vocabulary cross-entropy (csrc/lm_loss.hip): the caption loss of the BLIP text decoder
+# ------------------------------------------------------------------------------------------------
+IGNORE_INDEX = -100
+
+
+def check_vocab_labels(labels, V):
+    """the host-side refusal of a label that is neither in [0, V) nor IGNORE_INDEX, before anything is
+    launched (a device tensor is copied to the host for it: one synchronisation)"""
+    lab = labels.detach().cpu()
+    bad = (lab != IGNORE_INDEX) & ((lab < 0) | (lab >= V))
+    if bool(bad.any()):
+        raise ValueError(f"vocab_xent: label {int(lab[bad][0])} is neither in [0, {V}) nor {IGNORE_INDEX}")
+
+
+def _xent_args(logits, labels):
+    _require_cuda(logits, labels)
+    if logits.dtype != torch.float32:
+        raise ValueError("vocab_xent: logits must be fp32")
+    R, V = logits.shape
+    ld = _ld(logits)
+    if labels.dtype != torch.int64 or labels.dim() != 1 or labels.numel() != R or not labels.is_contiguous():
+        raise ValueError(f"vocab_xent: labels must be a contiguous int64 vector of {R} entries")
+    return R, V, ld
+
+
+def vocab_xent_fwd(logits, labels, eps=0.0, rows_per_seq=None, check_labels=True):
+    """CrossEntropyLoss(label_smoothing=eps, ignore_index=-100) of fp32 logits [R, V] (a row-major view, leading
+    dimension >= V) against int64 labels [R]: (loss_rows [R] (0 where ignored), lse [R], lse_lo [R], mean over the
+    valid rows (a 0-d tensor; NaN without one), n_valid (int64, 0-d), seq_sums [R / rows_per_seq] or None). All
+    fp32 device tensors; nothing visits the host unless `check_labels` (check_vocab_labels). `lse_lo` holds what
+    fp32 rounded away from lse (include/mmfd.h); vocab_xent_bwd takes the two together."""
+    R, V, ld = _xent_args(logits, labels)
+    if check_labels and V >= 1:
+        check_vocab_labels(labels, V)
+    dev = logits.device
+    loss_rows = torch.empty(R, device=dev, dtype=torch.float32)
+    lse = torch.empty(R, device=dev, dtype=torch.float32)
+    lse_lo = torch.empty(R, device=dev, dtype=torch.float32)
+    mean = torch.empty((), device=dev, dtype=torch.float32)
+    n_valid = torch.empty((), device=dev, dtype=torch.int64)
+    seq = torch.empty(R // rows_per_seq, device=dev, dtype=torch.float32) if rows_per_seq else None
+    _check(lib().mmfd_vocab_xent_fwd(R, V, _ptr(logits), ld, _ptr(labels), float(eps), int(rows_per_seq or 0),
+                                     _ptr(loss_rows), _ptr(lse), _ptr(lse_lo), _ptr(mean), _ptr(n_valid), _ptr(seq),
+                                     _stream()),
+           "mmfd_vocab_xent_fwd")
+    return loss_rows, lse, lse_lo, mean, n_valid, seq
+
+
+def vocab_xent_bwd(logits, labels, lse, lse_lo, eps, dtype, *, upstream=None, n_valid=None, rows_per_seq=None, out=None):
+    """dlogits [R, V] in `dtype` (fp32 / bf16) of vocab_xent_fwd's loss, from the forward's `lse` and `lse_lo`
+    (fp32 [R] each). Mean form: `n_valid` (the forward's device counter) and `upstream` a 1-element fp32 tensor or
+    None (= 1); per-sequence form: n_valid None, `upstream` fp32 [R / rows_per_seq] weights. `out`: a row-major
+    [R, V] view (leading dimension >= V) to write into; nothing is written past column V."""
+    R, V, ld = _xent_args(logits, labels)
+    for name, t in (("lse", lse), ("lse_lo", lse_lo)):
+        if t is None or t.dtype != torch.float32 or t.dim() != 1 or t.numel() != R or not t.is_contiguous():
+            raise ValueError(f"vocab_xent_bwd: {name} must be the forward's contiguous fp32 vector of {R} entries")
+    if out is None:
+        out = torch.empty((R, V), device=logits.device, dtype=dtype)
+    if out.dtype != dtype or out.shape[0] != R or out.shape[1] != V:
+        raise ValueError("vocab_xent_bwd: out must be [R, V] of the requested dtype")
+    if upstream is not None and (upstream.dtype != torch.float32 or not upstream.is_contiguous()):
+        raise ValueError("vocab_xent_bwd: upstream must be a contiguous fp32 tensor")
+    if n_valid is None and (upstream is None or not rows_per_seq or upstream.numel() * rows_per_seq != R):
+        raise ValueError("vocab_xent_bwd: the per-sequence form needs one upstream weight per rows_per_seq rows")
+    if n_valid is not None and (n_valid.dtype != torch.int64 or n_valid.numel() != 1):
+        raise ValueError("vocab_xent_bwd: n_valid must be the forward's int64 counter")
+    _require_cuda(lse, lse_lo, upstream, n_valid, out)
+    _check(lib().mmfd_vocab_xent_bwd(dtype_code(dtype), R, V, _ptr(logits), ld, _ptr(labels), _ptr(lse), _ptr(lse_lo), float(eps),
+                                     _ptr(upstream), _ptr(n_valid), int(rows_per_seq or 0), _ptr(out), _ld(out),
+                                     _stream()), "mmfd_vocab_xent_bwd")
+    return out

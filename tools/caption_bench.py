@@ -2,13 +2,18 @@
 shapes, random weights and pixels) and the LM-head kernel alone.
 
   python tools/caption_bench.py [--batches 1 20] [--num-beams 1] [--reps 3] [--out FILE]
+  python tools/caption_bench.py --loss [--batches 20] [--seq 21] [--reps 7] [--out FILE]
 
 Per (batch, precision): wall time of `generate` (20 new tokens; host-synchronised, the ids copied back)
 eager and as one graph replay, and per precision the device time of kernels.lm_head_argmax at
 V = 30524, K = 768 with the bytes it has to read (W + bias + x) per second. Prints one JSON line.
 Random weights seldom produce the stop token, so eager mode runs all 20 steps like the graph.
 --num-beams N > 1 times beam search instead (batch * N decoder rows) and, per precision and batch, the device time
-of one step's three beam kernel groups (selection, update, cache reorder at position 10) on the model's shapes."""
+of one step's three beam kernel groups (selection, update, cache reorder at position 10) on the model's shapes.
+--loss times the caption loss instead (forward(labels=), train_text_decoder, label smoothing 0.1): per precision
+and batch the wall time of the forward under no_grad and of forward + backward (host-synchronised, median of
+--reps runs after one warm-up), the vision tower's share (image_embeds alone), and the device time of the two
+vocabulary cross-entropy kernels on the model's [B * T, 30524] logits with the bytes they have to move."""
 import argparse
 import json
 import os
@@ -94,13 +99,96 @@ def beam_step_times(dt, B, nb, V=30524, E=768, L=12, steps=20, t=10, reps=20):
     return out
 
 
+def xent_times(dt, R, V=30524, reps=20):
+    """device time (us, median) of vocab_xent_fwd (both launches) and vocab_xent_bwd on random [R, V] logits, laid
+    out as the model lays them out: rows of vocab_ld(V) columns"""
+    from mmfd.blip import vocab_ld
+    ld = vocab_ld(V)
+    z = torch.randn(R, ld, device="cuda")[:, :V]
+    y = torch.randint(0, V, (R,), device="cuda")
+    rows, lse, lse_lo, mean, n_valid, _ = K.vocab_xent_fwd(z, y, 0.1, check_labels=False)
+    d = torch.zeros(R, ld, device="cuda", dtype=dt)[:, :V]
+    esz = d.element_size()
+    out = {"R": R, "V": V, "ld": ld, "fwd_bytes": R * V * 4, "bwd_bytes": R * V * (4 + esz)}
+    for name, fn, nbytes in (("fwd", lambda: K.vocab_xent_fwd(z, y, 0.1, check_labels=False), R * V * 4),
+                             ("bwd", lambda: K.vocab_xent_bwd(z, y, lse, lse_lo, 0.1, dt, n_valid=n_valid, out=d),
+                              R * V * (4 + esz))):
+        fn()
+        ts = []
+        for _ in range(reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1) * 1e-3)
+        med = sorted(ts)[len(ts) // 2]
+        out[name + "_us"] = round(med * 1e6, 1)
+        out[name + "_TBps"] = round(nbytes / med / 1e12, 3)
+    out["note"] = "warm: the logits (R * V * 4 bytes) fit the last-level cache when R * V * 4 < 256 MiB"
+    return out
+
+
+def loss_main(a):
+    from mmfd.blip import BlipConfig, lm_head_gemm_paths
+    torch.manual_seed(0)
+    m = BlipForConditionalGeneration(BlipConfig(train_text_decoder=True)).to("cuda").eval()
+    m.config.text.label_smoothing = 0.1
+    T = a.seq
+    res = {"loss": [], "xent": [], "T": T}
+    for prec, dt in (("fp32", torch.float32), ("bf16", torch.bfloat16)):
+        m.set_precision(prec)
+        for B in a.batches:
+            px = torch.randn(B, 3, 384, 384, device="cuda")
+            ids = torch.randint(1000, 30000, (B, T))
+            ids[:, 0] = m.config.text.bos_token_id
+
+            def fwd():
+                with torch.no_grad():
+                    return m(px, ids, labels=ids).loss
+
+            def fwd_bwd():
+                for p in m.parameters():
+                    p.grad = None
+                m(px, ids, labels=ids).loss.backward()
+
+            def vision():
+                return m.image_embeds(px)
+
+            row = {"precision": prec, "B": B, "T": T}
+            for name, fn in (("forward", fwd), ("forward_backward", fwd_bwd), ("vision_tower", vision)):
+                t_min, t_med = wall(fn, a.reps)
+                row[name + "_ms"], row[name + "_ms_min"] = round(t_med, 2), round(t_min, 2)
+            row["loss"] = round(float(fwd()), 4)
+            tc = m.config.text
+            row["lm_head_gemms"] = {k: v[1] for k, v in lm_head_gemm_paths(dt, B * T, tc.vocab_size, tc.hidden_size).items()}
+            res["loss"].append(row)
+            print(row, file=sys.stderr, flush=True)
+            res["xent"].append(dict(xent_times(dt, B * T), precision=prec))
+            print(res["xent"][-1], file=sys.stderr, flush=True)
+        m.invalidate_caches()
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 20])
     ap.add_argument("--num-beams", type=int, default=1)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--loss", action="store_true", help="time the caption loss (forward, forward + backward)")
+    ap.add_argument("--seq", type=int, default=21, help="--loss: tokens per caption")
     a = ap.parse_args()
+    if a.loss:
+        if a.batches == [1, 20]:
+            a.batches = [20]
+        a.reps = max(a.reps, 7)
+        return loss_main(a)
     torch.manual_seed(0)
     m = BlipForConditionalGeneration().to("cuda").eval()
     for p in m.parameters():
