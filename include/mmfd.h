@@ -575,6 +575,37 @@ int mmfd_beam_reorder(int64_t layers, int64_t rows, int64_t beam_rows, int64_t r
                       const void* const* src, void* const* dst, const int32_t* parent, mmfd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------- */
+/* Sampling for the same decoder (csrc/sample.hip): transformers' GenerationMixin._sample with   */
+/* do_sample=True as BLIP reaches it — temperature, top-k and top-p warpers in that order        */
+/* (min_tokens_to_keep = 1), softmax, one draw. Every length and the step number are host        */
+/* arguments; the seed is read on the device, so a captured graph replays with a new one.        */
+/* ------------------------------------------------------------------------------------------- */
+/* Per row r of logits fp32 [R][ldl] (V columns used):
+     s_i = logits[r][i] / temperature (one correctly rounded fp32 division). A NaN is never kept or drawn and
+       does not spoil its row; -inf has mass 0 and is never kept.
+     top-k, when 0 < top_k < V: tau = the top_k-th largest s counting duplicates; i is removed iff s_i < tau
+       (everything equal to tau stays).
+     top-p, when top_p < 1: m = max s, e_i = exp(s_i - m), S = sum e_i over the survivors; the survivors in
+       order (larger s first, equal s by the lower index); A_i = the mass strictly before i; i stays iff
+       A_i < top_p * S. The first entry always stays.
+     draw: S_k = the mass kept, u = (mmfd_hash(seed, step, row0 + r) >> 8) * 2^-24 (salt = step, index =
+       row0 + r; ctl = {seed, row0} in device memory); out_token[r] = the lowest kept index whose inclusive
+       prefix mass, in index order, exceeds u * S_k.
+     probs (optional, fp32 [R][ldp]): e_i / S_k for kept entries, 0 for the others; columns V .. ldp are not
+       touched. kept (optional, int32 [R]): the number of entries kept. A row without a number: token 0, kept 0.
+   The masses are the integers round(e_i * 2^40): all sums are integer sums, so the same inputs give the same
+   bits in every output, whatever the order of the workgroup's atomics. Any prefix mass and S are within
+   (31.5 + V * 2^-17) * 2^-24 (relative to S) of the exact values, 32 * 2^-24 up to V = 65536 (DESIGN section 9,
+   Sampling). One workgroup per row; rows of
+   V <= mmfd_sample_select_resident_max() keep their keys in LDS, longer ones re-read the logits on every
+   pass. V <= 2^20, R <= 65535; workspace >= mmfd_sample_select_workspace_bytes (never NULL). */
+int64_t mmfd_sample_select_resident_max(void);
+int64_t mmfd_sample_select_workspace_bytes(int64_t R, int64_t V);
+int mmfd_sample_select(int64_t R, int64_t V, const float* logits, int64_t ldl, float temperature, int64_t top_k,
+                       float top_p, const int64_t* ctl, int64_t step, int64_t* out_token, float* probs, int64_t ldp,
+                       int32_t* kept, void* workspace, int64_t workspace_bytes, mmfd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------- */
 /* Vocabulary cross-entropy (csrc/lm_loss.hip): the caption loss of the BLIP text decoder,      */
 /* transformers' BlipTextLMHeadModel with labels = CrossEntropyLoss(label_smoothing = eps,       */
 /* ignore_index = -100) over logits[:, :-1] / labels[:, 1:]. logits: fp32 [R][ldl], V columns    */

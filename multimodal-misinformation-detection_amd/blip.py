@@ -436,7 +436,8 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
 
     @torch.no_grad()
     def generate(self, pixel_values, input_ids=None, max_new_tokens=20, use_graph=True, num_beams=1,
-                 length_penalty=1.0, early_stopping=False):
+                 length_penalty=1.0, early_stopping=False, do_sample=False, temperature=1.0, top_k=0, top_p=1.0,
+                 num_return_sequences=1, seed=None, row_offset=0):
         """Captions, greedy (num_beams=1) or by beam search (below). Greedy: int64 [B, P + n] ids (the prompt, bos first, then n <= max_new_tokens generated
         tokens: a row that produced sep_token_id is padded with pad_token_id, and n is where the last row
         stopped) — the array transformers' `generate(pixel_values, input_ids)` returns by default.
@@ -448,9 +449,31 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
         array `generate(pixel_values, input_ids, num_beams=..., length_penalty=..., early_stopping=...,
         max_new_tokens=...)` returns there, unused positions filled as transformers fills them
         (`pad_token_id or sep_token_id`). `self.sequences_scores` then holds the fp32 scores [B] of the returned
-        hypotheses. Among equal scores the lower beam, then the lower token wins (torch.topk leaves that open)."""
+        hypotheses. Among equal scores the lower beam, then the lower token wins (torch.topk leaves that open).
+        do_sample=True: transformers' sampling — `temperature`, `top_k` (0: off) and `top_p` (1: off) filters in
+        that order, then one draw per row and step (csrc/sample.hip) — with `num_return_sequences` = n samples per
+        image: int64 [B * n, P + len], rows b*n .. b*n + n - 1 being the samples of image b (the vision tower and the
+        cross-attention K|V run once per image), padded like the greedy result; B * n <= 32. The draw of row r at
+        decoder step t is u = (mmfd_hash(seed, t, row_offset + r) >> 8) * 2^-24 (t counts the prompt's steps too):
+        a pure function of its arguments, so a call is reproducible, and a batch cut into chunks that pass their
+        first global row as `row_offset` draws what the whole batch would. seed=None takes one from torch's global
+        CPU generator (torch.manual_seed makes the call reproducible); `self.sample_seed` holds the seed used. A
+        new seed replays the captured graph. num_beams > 1 together with do_sample is refused."""
         tc = self.config.text
         B = int(pixel_values.shape[0])
+        n_ret = num_return_sequences
+        if int(n_ret) != n_ret or n_ret < 1:
+            raise ValueError(f"num_return_sequences must be an integer >= 1, got {n_ret!r}")
+        if do_sample:
+            if num_beams != 1:
+                raise ValueError("do_sample together with num_beams > 1 (beam sampling) is not implemented")
+            K.check_sampling(temperature, top_k, top_p)
+            if B * int(n_ret) > 32:
+                raise ValueError(f"sampling needs batch * num_return_sequences <= 32 (the LM head kernel's rows), got "
+                                 f"batch {B}, num_return_sequences {n_ret}")
+        elif n_ret != 1:
+            raise ValueError("num_return_sequences > 1 needs do_sample=True (one deterministic caption per image "
+                             "otherwise)")
         if early_stopping not in (False, True):
             raise ValueError(f"early_stopping must be False or True, got {early_stopping!r} ('never' is not implemented)")
         if int(num_beams) != num_beams or not 1 <= num_beams <= 8:
@@ -461,6 +484,9 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
         sc, dev = self._ctx()
         px = pixel_values.to(dev).float().contiguous()
         prompt = self._prompt(input_ids)
+        if do_sample:
+            return self._generate_sample(sc, dev, px, prompt, int(max_new_tokens), bool(use_graph), int(n_ret),
+                                         float(temperature), int(top_k), float(top_p), seed, int(row_offset))
         if num_beams > 1:
             return self._generate_beams(sc, dev, px, prompt, int(max_new_tokens), bool(use_graph), int(num_beams),
                                         float(length_penalty), bool(early_stopping))
@@ -507,6 +533,117 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
         with torch.cuda.graph(g):
             run(st, n_forced)
         st["graph"] = g
+
+    # ---- sampling ------------------------------------------------------------------------------------
+    def _sample_state(self, B, steps, dev, n, temperature, top_k, top_p):
+        """the device buffers of one (batch, samples per image, steps, precision, sampling parameters): what _state
+        holds for B * n rows, the fp32 logits of one step, the sampled tokens and the {seed, row offset} the
+        selection reads on the device"""
+        key = ("sample", B, n, steps, self.compute_dtype, str(dev), temperature, top_k, top_p)
+        st = self._states.get(key)
+        if st is not None:
+            return st
+        vc, tc = self.config.vision, self.config.text
+        dt, E, H = self.compute_dtype, tc.hidden_size, tc.num_attention_heads
+        Li = (vc.image_size // vc.patch_size) ** 2 + 1
+        R = B * n
+        Bp = max(R, 16)
+        st = dict(
+            B=B, Bp=Bp, R=R, n=n, steps=steps, Li=Li, temperature=temperature, top_k=top_k, top_p=top_p,
+            px=torch.zeros(B, vc.num_channels, vc.image_size, vc.image_size, device=dev),
+            seq=torch.zeros(steps + 1, Bp, dtype=torch.int64, device=dev),
+            forced=torch.zeros(steps + 1, R, dtype=torch.int64, device=dev),
+            pos=torch.arange(steps + 1, dtype=torch.int64, device=dev)[:, None].expand(steps + 1, Bp).contiguous(),
+            finished=torch.zeros(R, dtype=torch.int32, device=dev),
+            argmax=torch.zeros(R, dtype=torch.int64, device=dev),
+            token=torch.zeros(R, dtype=torch.int64, device=dev),
+            ctl=torch.zeros(2, dtype=torch.int64, device=dev),
+            self_kv=[torch.zeros(Bp, steps, 2 * E, device=dev, dtype=dt) for _ in range(tc.num_hidden_layers)],
+            cross_o=torch.zeros(Bp, E, device=dev, dtype=dt),
+            logits=torch.zeros(R, tc.vocab_size, device=dev),
+            graph=None, sig=None, n_forced=-1)
+        need = max(K.lib().mmfd_attn_decode_workspace_bytes(B, H, E // H, Li),
+                   K.lib().mmfd_attn_decode_workspace_bytes(R, H, E // H, Li),
+                   K.lib().mmfd_attn_decode_workspace_bytes(Bp, H, E // H, steps), 16)
+        st["attn_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+        need = K.lib().mmfd_lm_head_argmax_workspace_bytes(K.dtype_code(dt), R, tc.vocab_size, E)
+        if need <= 0:
+            raise ValueError(f"mmfd BLIP: the LM head kernel takes at most 32 rows and widths up to 1024 (fp32) / 2048 "
+                             f"(bf16), got {R} rows, width {E}")
+        st["lm_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+        st["smp_ws"] = torch.empty(K.sample_select_workspace_bytes(R, tc.vocab_size), dtype=torch.uint8, device=dev)
+        if len(self._states) >= 8:
+            self._states.clear()
+        self._states[key] = st
+        return st
+
+    def _sample_step(self, sc, st, cross, t, forced):
+        """the greedy step with the argmax replaced: the LM head writes the fp32 logits, sample_select draws the
+        row's token from them, and the unchanged greedy rule applies forced / finished / pad / eos. A forced step
+        needs no logits: its token is the prompt's."""
+        tc = self.config.text
+        R = st["R"]
+        g = self._hidden(sc, st, cross, t, st["self_kv"], st["n"])
+        if not forced:
+            K.lm_head_argmax(g[:R], sc.w(WORD), sc.P[HEAD + "bias"], out=st["argmax"], logits=st["logits"],
+                             workspace=st["lm_ws"])
+            K.sample_select(st["logits"], st["temperature"], st["top_k"], st["top_p"], st["ctl"], t, out=st["token"],
+                            workspace=st["smp_ws"])
+        K.greedy_select(st["token"], st["finished"], tc.sep_token_id, tc.pad_token_id, st["seq"][t + 1, :R],
+                        forced=st["forced"][t + 1] if forced else None)
+
+    def _sample_run(self, st, n_forced):
+        sc, _ = self._ctx()
+        cross = self._cross_kv(sc, self._vision(sc, st["px"]))
+        for t in range(st["steps"]):
+            self._sample_step(sc, st, cross, t, forced=t < n_forced)
+
+    def _sample_begin(self, st, seed, row_offset):
+        st["seq"].zero_()
+        st["seq"][0, :st["R"]].copy_(st["forced"][0])
+        st["finished"].zero_()
+        st["ctl"].copy_(torch.tensor([seed - (1 << 64) if seed >= (1 << 63) else seed, row_offset], dtype=torch.int64))
+
+    def _generate_sample(self, sc, dev, px, prompt, max_new_tokens, use_graph, n, temperature, top_k, top_p, seed,
+                         row_offset):
+        tc = self.config.text
+        B = px.shape[0]
+        n_forced = len(prompt) - 1
+        steps = n_forced + max_new_tokens
+        if max_new_tokens < 1 or steps + 1 > tc.max_position_embeddings:
+            raise ValueError(f"prompt ({len(prompt)}) + max_new_tokens ({max_new_tokens}) must lie in "
+                             f"[2, {tc.max_position_embeddings}]")
+        if row_offset < 0:
+            raise ValueError(f"row_offset must be >= 0, got {row_offset}")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.sample_seed = seed
+        st = self._sample_state(B, steps, dev, n, temperature, top_k, top_p)
+        if tuple(px.shape) != tuple(st["px"].shape):
+            raise ValueError(f"pixel_values must be {tuple(st['px'].shape)}, got {tuple(px.shape)}")
+        st["px"].copy_(px)
+        st["forced"].zero_()
+        st["forced"][:len(prompt)] = torch.tensor(prompt, dtype=torch.int64, device=dev)[:, None]
+        self._sample_begin(st, seed, row_offset)
+        R = st["R"]
+        if use_graph:
+            if st["graph"] is None or st["sig"] != self._signature() or st["n_forced"] != n_forced:
+                self._capture(st, n_forced, dev, run=self._sample_run)
+                self._sample_begin(st, seed, row_offset)
+            st["graph"].replay()
+            seq = st["seq"][:, :R].t().cpu()
+            done = seq[:, n_forced + 1:] == tc.sep_token_id
+            first = torch.where(done.any(1), done.int().argmax(1) + 1, torch.tensor(max_new_tokens))
+            return seq[:, :n_forced + 1 + int(first.max())].contiguous()
+        cross = self._cross_kv(sc, self._vision(sc, st["px"]))
+        last = steps
+        for t in range(steps):
+            self._sample_step(sc, st, cross, t, forced=t < n_forced)
+            if t >= n_forced and bool(st["finished"].all()):
+                last = t + 1
+                break
+        return st["seq"][:last + 1, :R].t().contiguous().cpu()
 
     # ---- beam search ---------------------------------------------------------------------------------
     def _beam_state(self, B, steps, dev, nb, lp, early):

@@ -5,9 +5,11 @@ processor.decode(out[0], skip_special_tokens=True)`) and the same call in src/de
 `Captioner` takes what the reference's processor takes — a PIL image, or a list of PIL images / uint8 HWC
 arrays, resized and normalised on the device by mmfd.preprocess.ImagePreprocessor("blip") bit for bit as
 transformers' BlipImageProcessor does it — or already preprocessed pixel tensors ([B, 3, S, S]). Decoding is
-greedy or, with num_beams > 1, transformers' beam search (mmfd.blip, csrc/beam.hip). `Captioner.score` gives the
-log-likelihood of given captions (the model's forward(labels=), csrc/lm_loss.hip): perplexity on held-out captions,
-re-scoring of hypotheses. Still to follow: the resumable CSV driver and sampling."""
+greedy, with num_beams > 1 transformers' beam search (mmfd.blip, csrc/beam.hip), or with do_sample=True
+transformers' temperature / top-k / top-p sampling with num_return_sequences captions per image (csrc/sample.hip:
+caption variants for augmentation, hypotheses for `score`). `Captioner.score` gives the log-likelihood of given
+captions (the model's forward(labels=), csrc/lm_loss.hip): perplexity on held-out captions, re-scoring of
+hypotheses. Still to follow: the resumable CSV driver."""
 from __future__ import annotations
 
 import torch
@@ -21,14 +23,28 @@ class Captioner:
     `batch_decode(ids, skip_special_tokens=True)` or `decode`; loaded by the caller from a local directory —
     nothing is fetched here). `images`: a pixel tensor [B, 3, S, S] / [3, S, S], a PIL image, or a list of PIL
     images / uint8 HWC arrays. The model takes at most 32 rows per call (32 // num_beams images): larger
-    batches run in chunks whose rows are padded with pad_token_id to one width."""
+    batches run in chunks whose rows are padded with pad_token_id to one width.
+    do_sample=True: num_return_sequences = n sampled captions per image, [B * n, ...] ids / a flat list of B * n
+    strings, image-major (rows b*n .. b*n + n - 1 belong to image b), as transformers' generate and batch_decode
+    return them. Chunks hold 32 // n images; every chunk gets the call's one seed (seed=None: drawn once per call
+    from torch's global CPU generator) and its first global row as `row_offset`, so the result is the concatenation
+    of those `generate` calls and does not depend on where the chunks are cut. `self.sample_seed`: the seed used."""
 
     def __init__(self, model: BlipForConditionalGeneration, tokenizer=None, max_new_tokens=20, use_graph=True,
-                 num_beams=1, length_penalty=1.0, early_stopping=False):
+                 num_beams=1, length_penalty=1.0, early_stopping=False, do_sample=False, temperature=1.0, top_k=0,
+                 top_p=1.0, num_return_sequences=1, seed=None):
         self.model = model.eval()
         self.tokenizer = tokenizer
         self.max_new_tokens, self.use_graph = int(max_new_tokens), bool(use_graph)
         self.num_beams, self.length_penalty, self.early_stopping = int(num_beams), float(length_penalty), early_stopping
+        self.do_sample, self.temperature, self.top_k, self.top_p = bool(do_sample), temperature, top_k, top_p
+        self.num_return_sequences, self.seed, self.sample_seed = int(num_return_sequences), seed, None
+        if self.num_return_sequences < 1 or self.num_return_sequences > 32:
+            raise ValueError(f"num_return_sequences must lie in [1, 32], got {num_return_sequences}")
+        if self.num_return_sequences > 1 and not self.do_sample:
+            raise ValueError("num_return_sequences > 1 needs do_sample=True")
+        if self.do_sample and self.num_beams != 1:
+            raise ValueError("do_sample together with num_beams > 1 (beam sampling) is not implemented")
         self._pre = None
 
     def pixels(self, images):
@@ -49,10 +65,19 @@ class Captioner:
         kw = dict(input_ids=input_ids, max_new_tokens=self.max_new_tokens, use_graph=self.use_graph)
         if self.num_beams != 1:
             kw.update(num_beams=self.num_beams, length_penalty=self.length_penalty, early_stopping=self.early_stopping)
-        chunk = max(1, 32 // max(1, self.num_beams))
+        n = self.num_return_sequences
+        if self.do_sample:
+            seed = self.seed
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+            self.sample_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+            kw.update(do_sample=True, temperature=self.temperature, top_k=self.top_k, top_p=self.top_p,
+                      num_return_sequences=n, seed=self.sample_seed)
+        chunk = max(1, 32 // max(1, self.num_beams, n))
         if px.shape[0] <= chunk:
             return self.model.generate(px, **kw)
-        outs = [self.model.generate(px[i:i + chunk], **kw) for i in range(0, px.shape[0], chunk)]
+        row = (lambda i: dict(row_offset=i * n)) if self.do_sample else (lambda i: {})
+        outs = [self.model.generate(px[i:i + chunk], **kw, **row(i)) for i in range(0, px.shape[0], chunk)]
         width = max(o.shape[1] for o in outs)
         pad = self.model.config.text.pad_token_id
         return torch.cat([torch.nn.functional.pad(o, (0, width - o.shape[1]), value=pad) for o in outs], 0)

@@ -221,6 +221,9 @@ SIGNATURES = {
     "mmfd_beam_select": (_I, [_I64, _I64, _I64, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
     "mmfd_beam_update": (_I, [_I64, _I64, _I64, _I64, _I64, _I, _I, _I64, _F] + [_VP] * 12 + [_I64, _VP]),
     "mmfd_beam_reorder": (_I, [_I64, _I64, _I64, _I64, _I64, _VP, _VP, _VP, _VP]),
+    "mmfd_sample_select_resident_max": (_I64, []),
+    "mmfd_sample_select_workspace_bytes": (_I64, [_I64, _I64]),
+    "mmfd_sample_select": (_I, [_I64, _I64, _VP, _I64, _F, _I64, _F, _VP, _I64, _VP, _VP, _I64, _VP, _VP, _I64, _VP]),
     "mmfd_vocab_xent_fwd": (_I, [_I64, _I64, _VP, _I64, _VP, _F, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mmfd_vocab_xent_bwd": (_I, [_I, _I64, _I64, _VP, _I64, _VP, _VP, _VP, _F, _VP, _VP, _I64, _VP, _I64, _VP]),
 }
@@ -1658,6 +1661,66 @@ def beam_reorder(src, dst, src_table, dst_table, parent, beam_rows, n_pos):
     es = a.element_size()
     _check(lib().mmfd_beam_reorder(len(src), rows, int(beam_rows), steps * width * es, int(n_pos) * width * es,
                                    _ptr(src_table), _ptr(dst_table), _ptr(parent), _stream()), "mmfd_beam_reorder")
+
+
+# ------------------------------------------------------------------------------------------------
+# sampling (csrc/sample.hip)
+# ------------------------------------------------------------------------------------------------
+def sample_select_resident_max():
+    """the longest row whose keys sample_select keeps in LDS (longer rows re-read the logits on every pass)"""
+    return int(lib().mmfd_sample_select_resident_max())
+
+
+def sample_select_workspace_bytes(R, V):
+    n = lib().mmfd_sample_select_workspace_bytes(int(R), int(V))
+    _check(0 if n > 0 else MMFD_ERR_INVALID, "mmfd_sample_select_workspace_bytes")
+    return int(n)
+
+
+def check_sampling(temperature, top_k, top_p):
+    """the host-side refusal of sampling parameters transformers' warpers refuse too"""
+    t, p = float(temperature), float(top_p)
+    if not (t > 0.0 and t != float("inf")):
+        raise ValueError(f"temperature must be a finite number > 0, got {temperature!r}")
+    if int(top_k) != top_k or top_k < 0:
+        raise ValueError(f"top_k must be an integer >= 0 (0: no filter), got {top_k!r}")
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"top_p must lie in [0, 1], got {top_p!r}")
+    return t, int(top_k), p
+
+
+def sample_select(logits, temperature, top_k, top_p, ctl, step, *, out=None, probs=None, kept=None, workspace=None):
+    """one sampled token per row of logits fp32 [R, V] (rows may be strided): temperature, top-k and top-p
+    filters in transformers' order, softmax, and one draw with u = (hash(seed, step, row0 + r) >> 8) * 2^-24
+    (include/mmfd.h mmfd_sample_select). ctl: int64 [2] device tensor {seed, row0}. Returns out int64 [R];
+    probs (fp32 [R, >= V] view, optional) receives the filtered distribution, kept (int32 [R], optional) the
+    number of entries that survived the filters. Equal logits are ordered by the lower index; a NaN is never
+    kept."""
+    _require_cuda(logits, ctl, out, probs, kept, workspace)
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("sample_select: logits must be an fp32 [R, V] view with a contiguous last dim")
+    R, V = logits.shape
+    t, k, p = check_sampling(temperature, top_k, top_p)
+    if ctl.dtype != torch.int64 or ctl.numel() != 2 or not ctl.is_contiguous():
+        raise ValueError("sample_select: ctl must be a contiguous int64 tensor {seed, row0}")
+    if int(step) < 0:
+        raise ValueError(f"sample_select: step = {step}")
+    if out is None:
+        out = torch.empty(R, device=logits.device, dtype=torch.int64)
+    if out.dtype != torch.int64 or tuple(out.shape) != (R,) or not out.is_contiguous():
+        raise ValueError(f"sample_select: out must be a contiguous int64 tensor of shape ({R},)")
+    if probs is not None and (probs.dtype != torch.float32 or probs.dim() != 2 or probs.shape[0] != R
+                              or probs.shape[1] < V or probs.stride(1) != 1):
+        raise ValueError("sample_select: probs must be an fp32 [R, >= V] view with a contiguous last dim")
+    if kept is not None:
+        _i32(kept, (R,), "sample_select: kept")
+    if workspace is None:
+        workspace = torch.empty(sample_select_workspace_bytes(R, V), device=logits.device, dtype=torch.uint8)
+    _check(lib().mmfd_sample_select(R, V, _ptr(logits), logits.stride(0), t, k, p, _ptr(ctl), int(step), _ptr(out),
+                                    _ptr(probs), probs.stride(0) if probs is not None else 0, _ptr(kept),
+                                    _ptr(workspace), workspace.numel() * workspace.element_size(), _stream()),
+           "mmfd_sample_select")
+    return out
 
 
 # ------------------------------------------------------------------------------------------------

@@ -3,6 +3,7 @@ shapes, random weights and pixels) and the LM-head kernel alone.
 
   python tools/caption_bench.py [--batches 1 20] [--num-beams 1] [--reps 3] [--out FILE]
   python tools/caption_bench.py --loss [--batches 20] [--seq 21] [--reps 7] [--out FILE]
+  python tools/caption_bench.py --sample [--top-k 50] [--top-p 0.9] [--temperature 1.0] [--num-return-sequences 1]
 
 Per (batch, precision): wall time of `generate` (20 new tokens; host-synchronised, the ids copied back)
 eager and as one graph replay, and per precision the device time of kernels.lm_head_argmax at
@@ -13,7 +14,11 @@ of one step's three beam kernel groups (selection, update, cache reorder at posi
 --loss times the caption loss instead (forward(labels=), train_text_decoder, label smoothing 0.1): per precision
 and batch the wall time of the forward under no_grad and of forward + backward (host-synchronised, median of
 --reps runs after one warm-up), the vision tower's share (image_embeds alone), and the device time of the two
-vocabulary cross-entropy kernels on the model's [B * T, 30524] logits with the bytes they have to move."""
+vocabulary cross-entropy kernels on the model's [B * T, 30524] logits with the bytes they have to move.
+--sample times `generate(do_sample=True, ...)` instead (batch * num_return_sequences decoder rows), eager and graph,
+with greedy decoding of as many rows in the same run as its yardstick, and `sample_step_times`: the device time of
+kernels.sample_select alone on [rows, 30524] logits for the call's filters and for each filter alone, beside
+kernels.beam_select at the same row count."""
 import argparse
 import json
 import os
@@ -97,6 +102,85 @@ def beam_step_times(dt, B, nb, V=30524, E=768, L=12, steps=20, t=10, reps=20):
             ts.append(e0.elapsed_time(e1) * 1e3)
         out[name] = round(sorted(ts)[len(ts) // 2], 1)
     return out
+
+
+def _device_us(fn, reps):
+    fn()
+    ts = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ts.append(e0.elapsed_time(e1) * 1e3)
+    return round(sorted(ts)[len(ts) // 2], 1)
+
+
+def sample_step_times(R, temperature, top_k, top_p, V=30524, reps=20):
+    """device time (us, median of reps, each between two events) of sample_select on random N(0, 1) logits [R, V]:
+    the call's filters, every filter alone, no filter, and the call's filters with the probabilities written; and
+    of beam_select over the same rows (3 beams per image when R is a multiple of 3, else 1)"""
+    dev = "cuda"
+    logits = torch.randn(R, V, device=dev)
+    ctl = torch.tensor([1234, 0], dtype=torch.int64, device=dev)
+    tok = torch.zeros(R, dtype=torch.int64, device=dev)
+    probs = torch.zeros(R, V, device=dev)
+    ws = torch.empty(K.sample_select_workspace_bytes(R, V), dtype=torch.uint8, device=dev)
+    out = {"rows": R, "V": V, "temperature": temperature, "top_k": top_k, "top_p": top_p}
+    cases = {"select_us": (temperature, top_k, top_p), "no_filter_us": (1.0, 0, 1.0), "temperature_only_us": (0.7, 0, 1.0),
+             "top_k_only_us": (1.0, 50, 1.0), "top_p_only_us": (1.0, 0, 0.9)}
+    for name, (t, k, p) in cases.items():
+        out[name] = _device_us(lambda: K.sample_select(logits, t, k, p, ctl, 3, out=tok, workspace=ws), reps)
+    out["select_with_probs_us"] = _device_us(
+        lambda: K.sample_select(logits, temperature, top_k, top_p, ctl, 3, out=tok, probs=probs, workspace=ws), reps)
+    nb = 3 if R % 3 == 0 else 1
+    running = -torch.rand(R, device=dev)
+    cand = K.beam_select(logits, running, nb)
+    bws = torch.empty(K.beam_select_workspace_bytes(R // nb, nb, V), dtype=torch.uint8, device=dev)
+    out["beam_select_us"] = _device_us(lambda: K.beam_select(logits, running, nb, out=cand, workspace=bws), reps)
+    out["beam_select_num_beams"] = nb
+    return out
+
+
+def sample_main(a):
+    torch.manual_seed(0)
+    m = BlipForConditionalGeneration().to("cuda").eval()
+    for p in m.parameters():
+        p.requires_grad_(False)
+    n = a.num_return_sequences
+    kw = dict(do_sample=True, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, num_return_sequences=n, seed=1)
+    res = {"generate": [], "sample_step_times": [], "sampling": {k: v for k, v in kw.items() if k != "do_sample"}}
+    for prec in ("fp32", "bf16"):
+        m.set_precision(prec)
+        for B in a.batches:
+            R = B * n
+            px = torch.randn(B, 3, 384, 384, device="cuda")
+            pxr = torch.randn(R, 3, 384, 384, device="cuda")
+            row = {"precision": prec, "B": B, "rows": R}
+            for mode, g in (("eager", False), ("graph", True)):
+                t_min, t_med = wall(lambda: m.generate(px, use_graph=g, **kw), a.reps)
+                row["sample_" + mode + "_ms"], row["sample_" + mode + "_ms_min"] = round(t_med, 2), round(t_min, 2)
+                t_min, t_med = wall(lambda: m.generate(pxr, use_graph=g), a.reps)
+                row["greedy_same_rows_" + mode + "_ms"] = round(t_med, 2)
+                row["greedy_same_rows_" + mode + "_ms_min"] = round(t_min, 2)
+                t_min, t_med = wall(lambda: m.generate(px, use_graph=g), a.reps)
+                row["greedy_same_images_" + mode + "_ms"] = round(t_med, 2)
+            row["tokens"] = int(m.generate(px, use_graph=True, **kw).shape[1]) - 1
+            row["note"] = ("greedy_same_rows runs the vision tower on `rows` images, sampling on B; greedy_same_images "
+                           "decodes B rows")
+            res["generate"].append(row)
+            print(row, file=sys.stderr, flush=True)
+            if prec == "fp32":  # the selection reads fp32 logits in both precisions
+                res["sample_step_times"].append(sample_step_times(R, a.temperature, a.top_k, a.top_p))
+                print(res["sample_step_times"][-1], file=sys.stderr, flush=True)
+        m.invalidate_caches()
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
 
 
 def xent_times(dt, R, V=30524, reps=20):
@@ -183,7 +267,14 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--loss", action="store_true", help="time the caption loss (forward, forward + backward)")
     ap.add_argument("--seq", type=int, default=21, help="--loss: tokens per caption")
+    ap.add_argument("--sample", action="store_true", help="time generate(do_sample=True) and sample_select")
+    ap.add_argument("--top-k", type=int, default=50)
+    ap.add_argument("--top-p", type=float, default=0.9)
+    ap.add_argument("--temperature", type=float, default=1.0)
+    ap.add_argument("--num-return-sequences", type=int, default=1)
     a = ap.parse_args()
+    if a.sample:
+        return sample_main(a)
     if a.loss:
         if a.batches == [1, 20]:
             a.batches = [20]
