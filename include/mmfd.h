@@ -538,7 +538,8 @@ int mmfd_greedy_select(int64_t B, const int64_t* argmax, const int64_t* forced, 
 
 /* ------------------------------------------------------------------------------------------- */
 /* Beam search for the same decoder (csrc/beam.hip): transformers' GenerationMixin._beam_search  */
-/* with one eos token, no logits processors and no sampling. B images of nb <= 8 beams each; row */
+/* with one eos token and no sampling; the logits processors of the section below enter through  */
+/* mmfd_row_log_softmax / mmfd_beam_select_logprobs. B images of nb <= 8 beams each; row         */
 /* b*nb + j is beam j of image b. Every length and the step number are host arguments.           */
 /* ------------------------------------------------------------------------------------------- */
 /* Candidate selection: for logits fp32 [B*nb][ldl] and running fp32 [B*nb], per image the 2 nb best
@@ -553,6 +554,20 @@ int64_t mmfd_beam_select_workspace_bytes(int64_t B, int64_t nb, int64_t V);
 int mmfd_beam_select(int64_t B, int64_t nb, int64_t V, const float* logits, int64_t ldl, const float* running,
                      float* out_score, int32_t* out_beam, int32_t* out_token, void* workspace,
                      int64_t workspace_bytes, mmfd_stream_t stream);
+/* The selection cut in two, for scores that are edited between the normalisation and the selection (transformers'
+   _beam_search hands log_softmax(logits) of every running beam to the logits processors, then adds the running
+   score). mmfd_row_log_softmax: logits[r][i] <- logits[r][i] - logsumexp(row r) in place, fp32 [R][ldl], the
+   log-sum-exp being the one mmfd_beam_select forms (a NaN left out and left a NaN); R <= 65535, V <= 2^20;
+   workspace 4-byte aligned, >= mmfd_row_log_softmax_workspace_bytes. mmfd_beam_select_logprobs: mmfd_beam_select
+   with score = logprobs[row][token] + running[row] and no normalisation: an entry no processor touched scores bit
+   for bit what mmfd_beam_select gives it. -inf candidates order as numbers (below every finite score, above NaN),
+   among themselves by the flat index: the indices stay valid and distinct. Workspace as mmfd_beam_select. */
+int64_t mmfd_row_log_softmax_workspace_bytes(int64_t R, int64_t V);
+int mmfd_row_log_softmax(int64_t R, int64_t V, float* logits, int64_t ldl, void* workspace, int64_t workspace_bytes,
+                         mmfd_stream_t stream);
+int mmfd_beam_select_logprobs(int64_t B, int64_t nb, int64_t V, const float* logprobs, int64_t ldl,
+                              const float* running, float* out_score, int32_t* out_beam, int32_t* out_token,
+                              void* workspace, int64_t workspace_bytes, mmfd_stream_t stream);
 /* One beam step on device state, from the candidates above (steps d - g of _beam_search). The step embeds
    position t and chooses the token of position t + 1 < T; gen_len = tokens generated once it is chosen;
    last != 0: position t + 1 is the last one (every candidate stops); len_div = gen_len ** length_penalty.
@@ -582,7 +597,9 @@ int mmfd_beam_reorder(int64_t layers, int64_t rows, int64_t beam_rows, int64_t r
 /* ------------------------------------------------------------------------------------------- */
 /* Per row r of logits fp32 [R][ldl] (V columns used):
      s_i = logits[r][i] / temperature (one correctly rounded fp32 division). A NaN is never kept or drawn and
-       does not spoil its row; -inf has mass 0 and is never kept.
+       does not spoil its row. A -inf entry (a column a logits processor banned) has mass exactly 0, is never
+       drawn, gets probability 0 in `probs` and is not counted in `kept`; where top_k reaches into the -inf
+       entries, tau is -inf and every number stays, as in transformers.
      top-k, when 0 < top_k < V: tau = the top_k-th largest s counting duplicates; i is removed iff s_i < tau
        (everything equal to tau stays).
      top-p, when top_p < 1: m = max s, e_i = exp(s_i - m), S = sum e_i over the survivors; the survivors in
@@ -604,6 +621,34 @@ int64_t mmfd_sample_select_workspace_bytes(int64_t R, int64_t V);
 int mmfd_sample_select(int64_t R, int64_t V, const float* logits, int64_t ldl, float temperature, int64_t top_k,
                        float top_p, const int64_t* ctl, int64_t step, int64_t* out_token, float* probs, int64_t ldp,
                        int32_t* kept, void* workspace, int64_t workspace_bytes, mmfd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------- */
+/* Logits processors for the same decoder (csrc/logits.hip): transformers' RepetitionPenalty-,   */
+/* NoRepeatNGram-, MinLength-, MinNewTokensLength- and SuppressTokensLogitsProcessor, applied in  */
+/* place to a row of fp32 scores from the row's own history on the device. What the scores are    */
+/* is the caller's: the raw logits for greedy decoding and sampling (the warpers of               */
+/* mmfd_sample_select run after the edits), mmfd_row_log_softmax's output for beam search.        */
+/* ------------------------------------------------------------------------------------------- */
+/* Per row r of scores [R][ldl] (V columns used), with the history h_i = history[r*hist_row_stride +
+   i*hist_pos_stride], i < cur_len <= 1024 (strides in elements of hist_elem_bytes = 8: int64, or 4: int32; the
+   prompt, bos first, is part of it):
+     penalty, when penalty != 1: every column that is some h_i becomes s < 0 ? s * penalty : s / penalty (IEEE
+       fp32), s the score as passed in — once, however often the id occurs (transformers gathers, then scatters).
+     then -inf into: the last id of every window h_i .. h_(i+n-1) whose first n - 1 ids equal the last n - 1 of
+       the history (n = ngram, 1 <= n <= cur_len; n = 1 bans every id seen; n = 0 or n > cur_len: nothing);
+       column eos when suppress_eos != 0 (the caller decides from min_length / min_new_tokens and the step:
+       cur_len < min_length or cur_len - prompt_len < min_new_tokens); the n_suppress <= 64 ids of the device list
+       `suppress` (int64; may be NULL when n_suppress = 0).
+   An id outside [0, V) touches nothing. At most cur_len + 1 + n_suppress columns are touched; no other column
+   is read. One workgroup per row. */
+int mmfd_logits_process(int64_t R, int64_t V, float* scores, int64_t ldl, const void* history,
+                        int64_t hist_row_stride, int64_t hist_pos_stride, int hist_elem_bytes, int64_t cur_len,
+                        float penalty, int64_t ngram, int suppress_eos, int64_t eos, const int64_t* suppress,
+                        int64_t n_suppress, mmfd_stream_t stream);
+/* out_idx[r] = argmax_i scores[r][i] over fp32 [R][ldl], V columns used: the largest number (-inf counts as
+   one), ties to the lowest index, a NaN never over a number (a row of nothing but NaN gives 0) — the order of
+   mmfd_lm_head_argmax, for scores that were edited after the LM head wrote them. One workgroup per row. */
+int mmfd_row_argmax(int64_t R, int64_t V, const float* scores, int64_t ldl, int64_t* out_idx, mmfd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------- */
 /* Vocabulary cross-entropy (csrc/lm_loss.hip): the caption loss of the BLIP text decoder,      */

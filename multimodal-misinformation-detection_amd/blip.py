@@ -283,9 +283,46 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
         weights and of the shadows / packed biases built from them (as predict.PairPredictor)"""
         return tuple((p.data_ptr(), p._version) for p in self.parameters())
 
-    def _state(self, B, steps, dev):
-        """the device buffers of one (batch, steps, precision): static inputs, caches, workspaces"""
-        key = (B, steps, self.compute_dtype, str(dev))
+    @staticmethod
+    def _proc_key(proc):
+        """what a state key carries of the logits processors: nothing when all are off (the keys, and so the
+        captured graphs, of a model that never uses them are what they were); else the launch scalars and the
+        LENGTH of the suppress list, whose ids live in a device buffer filled before every run"""
+        return () if proc is None else ("proc",) + tuple(proc[:4]) + (len(proc[4]),)
+
+    def _proc_buffers(self, st, proc, rows, dev):
+        """what a state with logits processors holds beside the others: the suppress list and, where the mode has
+        none yet (greedy), the fp32 logits of one step"""
+        if proc is None:
+            return
+        st["proc"] = proc
+        st["suppress"] = torch.zeros(max(1, len(proc[4])), dtype=torch.int64, device=dev)
+        if "logits" not in st:
+            st["logits"] = torch.zeros(rows, self.config.text.vocab_size, device=dev)
+
+    @staticmethod
+    def _proc_begin(st, proc, n_prompt):
+        """before a run: the prompt's length (min_new_tokens counts from it) and this call's suppress list"""
+        st["n_prompt"] = n_prompt
+        if proc is not None and proc[4]:
+            st["suppress"].copy_(torch.tensor(proc[4], dtype=torch.int64))
+
+    def _edit(self, st, scores, history, layout, t):
+        """the logits processors of step t on `scores` (csrc/logits.hip): the row's history holds positions 0 .. t.
+        Whether eos is banned is a host constant of the unrolled step, like every other length here."""
+        p, n, min_len, min_new, sup = st["proc"]
+        cur = t + 1
+        no_eos = cur < min_len or cur - st["n_prompt"] < min_new
+        if p == 1.0 and n == 0 and not no_eos and not sup:
+            return
+        K.logits_process(scores, history, cur, repetition_penalty=p, no_repeat_ngram_size=n, suppress_eos=no_eos,
+                         eos=self.config.text.sep_token_id, suppress=st["suppress"] if sup else None,
+                         n_suppress=len(sup), history_layout=layout)
+
+    def _state(self, B, steps, dev, proc=None):
+        """the device buffers of one (batch, steps, precision): static inputs, caches, workspaces; with logits
+        processors also the fp32 logits of one step and the suppress list"""
+        key = (B, steps, self.compute_dtype, str(dev)) + self._proc_key(proc)
         st = self._states.get(key)
         if st is not None:
             return st
@@ -315,6 +352,7 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
             raise ValueError(f"mmfd BLIP: the LM head kernel takes at most 32 rows and widths up to 1024 (fp32) / 2048 "
                              f"(bf16), got batch {B}, width {E}")
         st["lm_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+        self._proc_buffers(st, proc, B, dev)
         if len(self._states) >= 8:
             self._states.clear()
         self._states[key] = st
@@ -401,7 +439,17 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
         tc = self.config.text
         B, P = st["B"], sc.P
         g = self._hidden(sc, st, cross, t, st["self_kv"])
-        K.lm_head_argmax(g[:B], sc.w(WORD), P[HEAD + "bias"], out=st["argmax"], logits=logits, workspace=st["lm_ws"])
+        if st.get("proc") is None or logits is not None:
+            K.lm_head_argmax(g[:B], sc.w(WORD), P[HEAD + "bias"], out=st["argmax"], logits=logits,
+                             workspace=st["lm_ws"])
+        elif not forced:
+            # logits processors: the LM head stores its fp32 logits, the edits run on them, and the argmax is taken
+            # of the edited row (a fix-up of the fused argmax would not do: were the raw winner an edited column,
+            # the best unedited one would be unknown). A forced step needs neither: its token is the prompt's.
+            K.lm_head_argmax(g[:B], sc.w(WORD), P[HEAD + "bias"], out=st["argmax"], logits=st["logits"],
+                             workspace=st["lm_ws"])
+            self._edit(st, st["logits"], st["seq"], "steps", t)
+            K.row_argmax(st["logits"], out=st["argmax"])
         if select:
             K.greedy_select(st["argmax"], st["finished"], tc.sep_token_id, tc.pad_token_id, st["seq"][t + 1, :B],
                             forced=st["forced"][t + 1] if forced else None)
@@ -437,7 +485,8 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
     @torch.no_grad()
     def generate(self, pixel_values, input_ids=None, max_new_tokens=20, use_graph=True, num_beams=1,
                  length_penalty=1.0, early_stopping=False, do_sample=False, temperature=1.0, top_k=0, top_p=1.0,
-                 num_return_sequences=1, seed=None, row_offset=0):
+                 num_return_sequences=1, seed=None, row_offset=0, repetition_penalty=1.0, no_repeat_ngram_size=0,
+                 min_length=0, min_new_tokens=0, suppress_tokens=None):
         """Captions, greedy (num_beams=1) or by beam search (below). Greedy: int64 [B, P + n] ids (the prompt, bos first, then n <= max_new_tokens generated
         tokens: a row that produced sep_token_id is padded with pad_token_id, and n is where the last row
         stopped) — the array transformers' `generate(pixel_values, input_ids)` returns by default.
@@ -458,9 +507,26 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
         a pure function of its arguments, so a call is reproducible, and a batch cut into chunks that pass their
         first global row as `row_offset` draws what the whole batch would. seed=None takes one from torch's global
         CPU generator (torch.manual_seed makes the call reproducible); `self.sample_seed` holds the seed used. A
-        new seed replays the captured graph. num_beams > 1 together with do_sample is refused."""
+        new seed replays the captured graph. num_beams > 1 together with do_sample is refused.
+        Logits processors, in all three modes, with transformers' names, defaults (off) and rules, applied on the
+        device (csrc/logits.hip) from each row's own history, the prompt included:
+        `repetition_penalty` p > 0: the score s of every id the row already holds becomes s * p (s < 0) or s / p, once
+        however often the id occurs; `no_repeat_ngram_size` n: an id that would complete an n-gram the row already
+        holds is banned (-inf); `min_length` / `min_new_tokens`: sep_token_id is banned while the row holds fewer
+        than min_length ids (prompt and bos counted) or fewer than min_new_tokens generated ones (either rule bans:
+        where both are given and min_length > prompt + min_new_tokens, transformers lets min_new_tokens replace
+        min_length); `suppress_tokens`: up to 64 ids banned at every step. The penalty comes first, the bans after it.
+        Greedy decoding and sampling edit the raw logits (the sampling filters run afterwards, and a banned id has
+        probability 0); beam search edits log_softmax(logits) of every running beam before the running score is
+        added, as transformers does. min_new_tokens > max_new_tokens is accepted: the row runs to the last step. A
+        new suppress list of the same length, like a new seed, replays the captured graph; the other values are
+        launch constants and part of the graph's key."""
         tc = self.config.text
         B = int(pixel_values.shape[0])
+        proc = K.check_processors(repetition_penalty, no_repeat_ngram_size, min_length, min_new_tokens, suppress_tokens,
+                                  tc.vocab_size)
+        if proc == (1.0, 0, 0, 0, ()):
+            proc = None
         n_ret = num_return_sequences
         if int(n_ret) != n_ret or n_ret < 1:
             raise ValueError(f"num_return_sequences must be an integer >= 1, got {n_ret!r}")
@@ -486,22 +552,23 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
         prompt = self._prompt(input_ids)
         if do_sample:
             return self._generate_sample(sc, dev, px, prompt, int(max_new_tokens), bool(use_graph), int(n_ret),
-                                         float(temperature), int(top_k), float(top_p), seed, int(row_offset))
+                                         float(temperature), int(top_k), float(top_p), seed, int(row_offset), proc)
         if num_beams > 1:
             return self._generate_beams(sc, dev, px, prompt, int(max_new_tokens), bool(use_graph), int(num_beams),
-                                        float(length_penalty), bool(early_stopping))
+                                        float(length_penalty), bool(early_stopping), proc)
         n_forced = len(prompt) - 1
         steps = n_forced + int(max_new_tokens)
         if steps < 1 or steps + 1 > tc.max_position_embeddings:
             raise ValueError(f"prompt ({len(prompt)}) + max_new_tokens ({max_new_tokens}) must lie in "
                              f"[2, {tc.max_position_embeddings}]")
-        st = self._state(B, steps, dev)
+        st = self._state(B, steps, dev, proc)
         if tuple(px.shape) != tuple(st["px"].shape):
             raise ValueError(f"pixel_values must be {tuple(st['px'].shape)}, got {tuple(px.shape)}")
         st["px"].copy_(px)
         st["forced"].zero_()
         st["forced"][:len(prompt)] = torch.tensor(prompt, dtype=torch.int64, device=dev)[:, None]
         self._begin(st, st["forced"][0])
+        self._proc_begin(st, proc, len(prompt))
         if use_graph:
             if st["graph"] is None or st["sig"] != self._signature() or st["n_forced"] != n_forced:
                 self._capture(st, n_forced, dev)
@@ -535,11 +602,11 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
         st["graph"] = g
 
     # ---- sampling ------------------------------------------------------------------------------------
-    def _sample_state(self, B, steps, dev, n, temperature, top_k, top_p):
+    def _sample_state(self, B, steps, dev, n, temperature, top_k, top_p, proc=None):
         """the device buffers of one (batch, samples per image, steps, precision, sampling parameters): what _state
         holds for B * n rows, the fp32 logits of one step, the sampled tokens and the {seed, row offset} the
         selection reads on the device"""
-        key = ("sample", B, n, steps, self.compute_dtype, str(dev), temperature, top_k, top_p)
+        key = ("sample", B, n, steps, self.compute_dtype, str(dev), temperature, top_k, top_p) + self._proc_key(proc)
         st = self._states.get(key)
         if st is not None:
             return st
@@ -572,6 +639,7 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
                              f"(bf16), got {R} rows, width {E}")
         st["lm_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
         st["smp_ws"] = torch.empty(K.sample_select_workspace_bytes(R, tc.vocab_size), dtype=torch.uint8, device=dev)
+        self._proc_buffers(st, proc, R, dev)
         if len(self._states) >= 8:
             self._states.clear()
         self._states[key] = st
@@ -587,6 +655,8 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
         if not forced:
             K.lm_head_argmax(g[:R], sc.w(WORD), sc.P[HEAD + "bias"], out=st["argmax"], logits=st["logits"],
                              workspace=st["lm_ws"])
+            if st.get("proc") is not None:  # the processors come before the warpers, as in transformers
+                self._edit(st, st["logits"], st["seq"], "steps", t)
             K.sample_select(st["logits"], st["temperature"], st["top_k"], st["top_p"], st["ctl"], t, out=st["token"],
                             workspace=st["smp_ws"])
         K.greedy_select(st["token"], st["finished"], tc.sep_token_id, tc.pad_token_id, st["seq"][t + 1, :R],
@@ -605,7 +675,7 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
         st["ctl"].copy_(torch.tensor([seed - (1 << 64) if seed >= (1 << 63) else seed, row_offset], dtype=torch.int64))
 
     def _generate_sample(self, sc, dev, px, prompt, max_new_tokens, use_graph, n, temperature, top_k, top_p, seed,
-                         row_offset):
+                         row_offset, proc=None):
         tc = self.config.text
         B = px.shape[0]
         n_forced = len(prompt) - 1
@@ -619,13 +689,14 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.sample_seed = seed
-        st = self._sample_state(B, steps, dev, n, temperature, top_k, top_p)
+        st = self._sample_state(B, steps, dev, n, temperature, top_k, top_p, proc)
         if tuple(px.shape) != tuple(st["px"].shape):
             raise ValueError(f"pixel_values must be {tuple(st['px'].shape)}, got {tuple(px.shape)}")
         st["px"].copy_(px)
         st["forced"].zero_()
         st["forced"][:len(prompt)] = torch.tensor(prompt, dtype=torch.int64, device=dev)[:, None]
         self._sample_begin(st, seed, row_offset)
+        self._proc_begin(st, proc, len(prompt))
         R = st["R"]
         if use_graph:
             if st["graph"] is None or st["sig"] != self._signature() or st["n_forced"] != n_forced:
@@ -646,11 +717,11 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
         return st["seq"][:last + 1, :R].t().contiguous().cpu()
 
     # ---- beam search ---------------------------------------------------------------------------------
-    def _beam_state(self, B, steps, dev, nb, lp, early):
+    def _beam_state(self, B, steps, dev, nb, lp, early, proc=None):
         """the device buffers of one (batch, steps, precision, beam parameters): what _state holds for B * nb rows,
         a second set of self-attention caches (the reorder gathers from one into the other), the fp32 logits of
         one step and the search state of csrc/beam.hip"""
-        key = (B, steps, self.compute_dtype, str(dev), nb, lp, early)
+        key = (B, steps, self.compute_dtype, str(dev), nb, lp, early) + self._proc_key(proc)
         st = self._states.get(key)
         if st is not None:
             return st
@@ -686,6 +757,7 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
                              f"(bf16), got {R} rows, width {E}")
         st["lm_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
         st["sel_ws"] = torch.empty(K.beam_select_workspace_bytes(B, nb, tc.vocab_size), dtype=torch.uint8, device=dev)
+        self._proc_buffers(st, proc, R, dev)
         if len(self._states) >= 8:
             self._states.clear()
         self._states[key] = st
@@ -733,7 +805,17 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
                 continue
             K.lm_head_argmax(g[:R], sc.w(WORD), sc.P[HEAD + "bias"], out=st["argmax"], logits=st["logits"],
                              workspace=st["lm_ws"])
-            K.beam_select(st["logits"], st["beam"]["run_score"].view(-1), nb, out=st["cand"], workspace=st["sel_ws"])
+            if st.get("proc") is None:
+                K.beam_select(st["logits"], st["beam"]["run_score"].view(-1), nb, out=st["cand"],
+                              workspace=st["sel_ws"])
+            else:
+                # transformers hands log_softmax(logits) of every running beam to the processors and adds the running
+                # score afterwards: normalise once (over the unprocessed row), edit from the beam's own sequence as
+                # the last update left it, select without a second normalisation
+                K.row_log_softmax(st["logits"], workspace=st["sel_ws"])
+                self._edit(st, st["logits"], st["beam"]["run_seq"].view(R, steps + 1), "rows", t)
+                K.beam_select_logprobs(st["logits"], st["beam"]["run_score"].view(-1), nb, out=st["cand"],
+                                       workspace=st["sel_ws"])
             K.beam_update(st["cand"], st["beam"], t, n_forced, t + 1 == steps, tc.sep_token_id, st["lp"], st["early"],
                           st["seq"][t + 1, :R])
             if t + 1 < steps:
@@ -743,7 +825,7 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
             if eager and not self._beam_unfinished(st):
                 break
 
-    def _generate_beams(self, sc, dev, px, prompt, max_new_tokens, use_graph, nb, lp, early):
+    def _generate_beams(self, sc, dev, px, prompt, max_new_tokens, use_graph, nb, lp, early, proc=None):
         tc = self.config.text
         B = px.shape[0]
         n_forced = len(prompt) - 1
@@ -751,11 +833,12 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
         if max_new_tokens < 1 or steps + 1 > tc.max_position_embeddings:
             raise ValueError(f"prompt ({len(prompt)}) + max_new_tokens ({max_new_tokens}) must lie in "
                              f"[2, {tc.max_position_embeddings}]")
-        st = self._beam_state(B, steps, dev, nb, lp, early)
+        st = self._beam_state(B, steps, dev, nb, lp, early, proc)
         if tuple(px.shape) != tuple(st["px"].shape):
             raise ValueError(f"pixel_values must be {tuple(st['px'].shape)}, got {tuple(px.shape)}")
         st["px"].copy_(px)
         self._beam_begin(st, prompt)
+        self._proc_begin(st, proc, len(prompt))
         if use_graph:
             if st["graph"] is None or st["sig"] != self._signature() or st["n_forced"] != n_forced:
                 self._capture(st, n_forced, dev, run=self._beam_run)

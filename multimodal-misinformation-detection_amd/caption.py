@@ -9,11 +9,14 @@ greedy, with num_beams > 1 transformers' beam search (mmfd.blip, csrc/beam.hip),
 transformers' temperature / top-k / top-p sampling with num_return_sequences captions per image (csrc/sample.hip:
 caption variants for augmentation, hypotheses for `score`). `Captioner.score` gives the log-likelihood of given
 captions (the model's forward(labels=), csrc/lm_loss.hip): perplexity on held-out captions, re-scoring of
-hypotheses. Still to follow: the resumable CSV driver."""
+hypotheses. `repetition_penalty`, `no_repeat_ngram_size`, `min_length`, `min_new_tokens` and `suppress_tokens` are
+transformers' logits processors, on the device in every decoding mode (csrc/logits.hip): what keeps a caption from
+looping or stopping after three words. Still to follow: the resumable CSV driver."""
 from __future__ import annotations
 
 import torch
 
+from . import kernels as K
 from .blip import BlipForConditionalGeneration
 
 
@@ -32,7 +35,8 @@ class Captioner:
 
     def __init__(self, model: BlipForConditionalGeneration, tokenizer=None, max_new_tokens=20, use_graph=True,
                  num_beams=1, length_penalty=1.0, early_stopping=False, do_sample=False, temperature=1.0, top_k=0,
-                 top_p=1.0, num_return_sequences=1, seed=None):
+                 top_p=1.0, num_return_sequences=1, seed=None, repetition_penalty=1.0, no_repeat_ngram_size=0,
+                 min_length=0, min_new_tokens=0, suppress_tokens=None):
         self.model = model.eval()
         self.tokenizer = tokenizer
         self.max_new_tokens, self.use_graph = int(max_new_tokens), bool(use_graph)
@@ -45,6 +49,14 @@ class Captioner:
             raise ValueError("num_return_sequences > 1 needs do_sample=True")
         if self.do_sample and self.num_beams != 1:
             raise ValueError("do_sample together with num_beams > 1 (beam sampling) is not implemented")
+        # transformers' logits processors (mmfd.blip generate, csrc/logits.hip); checked here so that a bad value is
+        # refused where it is given. Only the ones that are on are passed on: a captioner without them calls
+        # generate as it always did
+        p, n, ml, mn, sup = K.check_processors(repetition_penalty, no_repeat_ngram_size, min_length, min_new_tokens,
+                                               suppress_tokens, model.config.text.vocab_size)
+        self.processors = {k: v for k, v, off in (("repetition_penalty", p, 1.0), ("no_repeat_ngram_size", n, 0),
+                                                  ("min_length", ml, 0), ("min_new_tokens", mn, 0),
+                                                  ("suppress_tokens", list(sup), [])) if v != off}
         self._pre = None
 
     def pixels(self, images):
@@ -62,7 +74,7 @@ class Captioner:
     @torch.no_grad()
     def generate_ids(self, pixel_values, input_ids=None):
         px = self.pixels(pixel_values)
-        kw = dict(input_ids=input_ids, max_new_tokens=self.max_new_tokens, use_graph=self.use_graph)
+        kw = dict(input_ids=input_ids, max_new_tokens=self.max_new_tokens, use_graph=self.use_graph, **self.processors)
         if self.num_beams != 1:
             kw.update(num_beams=self.num_beams, length_penalty=self.length_penalty, early_stopping=self.early_stopping)
         n = self.num_return_sequences

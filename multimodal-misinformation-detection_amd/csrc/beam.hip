@@ -6,6 +6,11 @@
 //                       leaves the {max, sum exp} of one slab of one row; (b) every workgroup combines its
 //                       row's partials into the log-sum-exp, scores its slab and leaves the slab's 2 nb best;
 //                       (c) one workgroup per image merges the lists of its nb rows.
+//   mmfd_row_log_softmax, mmfd_beam_select_logprobs   the same selection cut in two for the logits processors
+//                       (logits.hip), which transformers applies to log_softmax(logits) of every running beam
+//                       before the running score is added: (a) and an in-place x - lse over the same slabs with
+//                       the same log-sum-exp, then — after the edits — (b) without a second normalisation and (c).
+//                       An unedited entry scores bit for bit what mmfd_beam_select gives it.
 //   mmfd_beam_update    one workgroup per image: the next running beams, the finished hypotheses, the early-stop
 //                       heuristic, the parent row of every beam and the token the next step embeds.
 //   mmfd_beam_reorder   the self-attention caches of all layers gathered by parent row into a second set of
@@ -104,8 +109,24 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_partial_kernel(const float*
   }
 }
 
+// the row's log-sum-exp from its S partials: every thread of every workgroup of the row adds them in the same
+// order, so the whole row is scored against one value
+__device__ __forceinline__ float beam_row_lse(const float* __restrict__ pm, const float* __restrict__ ps, int row,
+                                              int S) {
+  float M = -INFINITY;
+  for (int s = 0; s < S; ++s) M = fmaxf(M, pm[(int64_t)row * S + s]);
+  float sum = 0.f;
+  for (int s = 0; s < S; ++s) {
+    const float m = pm[(int64_t)row * S + s];
+    if (m != -INFINITY) sum += ps[(int64_t)row * S + s] * expf(m - M);
+  }
+  return M + logf(sum);
+}
+
 // (b) grid (S, R): keys[(row * S + slab) * K + k], k < K = 2 nb: the slab's best scores in order (index = token);
-// 0 where the slab has fewer than K entries
+// 0 where the slab has fewer than K entries. LOGP: the row holds log-probabilities already (processed ones):
+// score = x + running, and pm / ps are not read
+template <bool LOGP>
 __global__ __launch_bounds__(BEAM_THREADS) void beam_slab_topk_kernel(const float* __restrict__ logits, int64_t ldl,
                                                                        const float* __restrict__ running, int V,
                                                                        int slab, int K, const float* __restrict__ pm,
@@ -114,23 +135,14 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_slab_topk_kernel(const floa
   __shared__ uint64_t sh[BEAM_WAVES];
   const int row = blockIdx.y, S = gridDim.x;
   const int lo = blockIdx.x * slab, hi = min(V, lo + slab);
-  // the row's log-sum-exp from its S partials: every thread of every workgroup of the row adds them in the
-  // same order, so the whole row is scored against one value
-  float M = -INFINITY;
-  for (int s = 0; s < S; ++s) M = fmaxf(M, pm[(int64_t)row * S + s]);
-  float sum = 0.f;
-  for (int s = 0; s < S; ++s) {
-    const float m = pm[(int64_t)row * S + s];
-    if (m != -INFINITY) sum += ps[(int64_t)row * S + s] * expf(m - M);
-  }
-  const float lse = M + logf(sum);
+  const float lse = LOGP ? 0.f : beam_row_lse(pm, ps, row, S);
   const float run = running[row];
   const float* x = logits + (int64_t)row * ldl;
   uint64_t key[BEAM_PER_THREAD];
 #pragma unroll
   for (int j = 0; j < BEAM_PER_THREAD; ++j) {
     const int i = lo + threadIdx.x + j * BEAM_THREADS;
-    key[j] = i < hi ? beam_key((x[i] - lse) + run, (uint32_t)i) : 0ull;
+    key[j] = i < hi ? beam_key(LOGP ? x[i] + run : (x[i] - lse) + run, (uint32_t)i) : 0ull;
   }
   uint64_t prev = ~0ull;
   for (int k = 0; k < K; ++k) {
@@ -142,6 +154,18 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_slab_topk_kernel(const floa
     if (threadIdx.x == 0) keys[((int64_t)row * S + blockIdx.x) * K + k] = best;
     prev = best;  // (0 once the slab is used up: nothing lies below it)
   }
+}
+
+// grid (S, R): x <- x - logsumexp(row) in place over one slab of one row, the value (b) scores against (a NaN
+// stays a NaN, -inf stays -inf). Reads only the partials of (a) beside its own slab.
+__global__ __launch_bounds__(BEAM_THREADS) void beam_normalize_kernel(float* __restrict__ logits, int64_t ldl, int V,
+                                                                       int slab, const float* __restrict__ pm,
+                                                                       const float* __restrict__ ps) {
+  const int row = blockIdx.y, S = gridDim.x;
+  const int lo = blockIdx.x * slab, hi = min(V, lo + slab);
+  const float lse = beam_row_lse(pm, ps, row, S);
+  float* x = logits + (int64_t)row * ldl;
+  for (int i = lo + threadIdx.x; i < hi; i += BEAM_THREADS) x[i] = x[i] - lse;
 }
 
 // (c) one workgroup per image over the nb * S * K keys of its rows, re-keyed by the flat index beam * V + token
@@ -331,18 +355,19 @@ extern "C" int64_t mmfd_beam_select_workspace_bytes(int64_t B, int64_t nb, int64
   return R * S * 8 + R * S * 2 * nb * 8;  // {max, sum} and 2 nb keys per (row, slab)
 }
 
-extern "C" int mmfd_beam_select(int64_t B, int64_t nb, int64_t V, const float* logits, int64_t ldl,
-                                const float* running, float* out_score, int32_t* out_beam, int32_t* out_token,
-                                void* workspace, int64_t workspace_bytes, mmfd_stream_t stream) {
-  MMFD_CHECK_ARG(nb >= 1 && nb <= BEAM_MAX_NB, "mmfd_beam_select: num_beams = %lld (1 .. %d)", (long long)nb,
-                 BEAM_MAX_NB);
-  MMFD_CHECK_ARG(B >= 1 && B * nb <= 65535, "mmfd_beam_select: B = %lld", (long long)B);
-  MMFD_CHECK_ARG(V >= 2 * nb && V <= (1 << 20), "mmfd_beam_select: V = %lld (2 num_beams .. 2^20)", (long long)V);
-  MMFD_CHECK_ARG(logits && running && out_score && out_beam && out_token, "mmfd_beam_select: null pointer");
-  MMFD_CHECK_ARG(ldl >= V, "mmfd_beam_select: leading dimension too small");
+namespace {
+
+int beam_select_run(const char* name, bool logp, int64_t B, int64_t nb, int64_t V, const float* logits, int64_t ldl,
+                    const float* running, float* out_score, int32_t* out_beam, int32_t* out_token, void* workspace,
+                    int64_t workspace_bytes, mmfd_stream_t stream) {
+  MMFD_CHECK_ARG(nb >= 1 && nb <= BEAM_MAX_NB, "%s: num_beams = %lld (1 .. %d)", name, (long long)nb, BEAM_MAX_NB);
+  MMFD_CHECK_ARG(B >= 1 && B * nb <= 65535, "%s: B = %lld", name, (long long)B);
+  MMFD_CHECK_ARG(V >= 2 * nb && V <= (1 << 20), "%s: V = %lld (2 num_beams .. 2^20)", name, (long long)V);
+  MMFD_CHECK_ARG(logits && running && out_score && out_beam && out_token, "%s: null pointer", name);
+  MMFD_CHECK_ARG(ldl >= V, "%s: leading dimension too small", name);
   const int64_t need = mmfd_beam_select_workspace_bytes(B, nb, V);
   MMFD_CHECK_ARG(workspace && workspace_bytes >= need && ((uintptr_t)workspace & 7) == 0,
-                 "mmfd_beam_select: needs an 8-byte aligned workspace of %lld bytes (mmfd_beam_select_workspace_bytes)",
+                 "%s: needs an 8-byte aligned workspace of %lld bytes (mmfd_beam_select_workspace_bytes)", name,
                  (long long)need);
   const int slab = beam_slab(V);
   const int64_t S = (V + slab - 1) / slab, R = B * nb;
@@ -351,14 +376,69 @@ extern "C" int mmfd_beam_select(int64_t B, int64_t nb, int64_t V, const float* l
   float* ps = pm + R * S;
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)S, (unsigned)R), block(BEAM_THREADS);
-  hipLaunchKernelGGL(beam_partial_kernel, grid, block, 0, s, logits, ldl, (int)V, slab, pm, ps);
-  MMFD_CHECK_LAUNCH("mmfd_beam_select (partials)");
-  hipLaunchKernelGGL(beam_slab_topk_kernel, grid, block, 0, s, logits, ldl, running, (int)V, slab, (int)(2 * nb), pm, ps,
-                     keys);
+  if (!logp) {
+    hipLaunchKernelGGL(beam_partial_kernel, grid, block, 0, s, logits, ldl, (int)V, slab, pm, ps);
+    MMFD_CHECK_LAUNCH("mmfd_beam_select (partials)");
+    hipLaunchKernelGGL(beam_slab_topk_kernel<false>, grid, block, 0, s, logits, ldl, running, (int)V, slab,
+                       (int)(2 * nb), pm, ps, keys);
+  } else {
+    hipLaunchKernelGGL(beam_slab_topk_kernel<true>, grid, block, 0, s, logits, ldl, running, (int)V, slab,
+                       (int)(2 * nb), pm, ps, keys);
+  }
   MMFD_CHECK_LAUNCH("mmfd_beam_select (slabs)");
   hipLaunchKernelGGL(beam_merge_kernel, dim3((unsigned)B), block, 0, s, keys, (int)nb, (int)S, (int)(2 * nb), (int)V,
                      out_score, out_beam, out_token);
   MMFD_CHECK_LAUNCH("mmfd_beam_select (merge)");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int mmfd_beam_select(int64_t B, int64_t nb, int64_t V, const float* logits, int64_t ldl,
+                                const float* running, float* out_score, int32_t* out_beam, int32_t* out_token,
+                                void* workspace, int64_t workspace_bytes, mmfd_stream_t stream) {
+  return beam_select_run("mmfd_beam_select", false, B, nb, V, logits, ldl, running, out_score, out_beam, out_token,
+                         workspace, workspace_bytes, stream);
+}
+
+extern "C" int mmfd_beam_select_logprobs(int64_t B, int64_t nb, int64_t V, const float* logprobs, int64_t ldl,
+                                         const float* running, float* out_score, int32_t* out_beam,
+                                         int32_t* out_token, void* workspace, int64_t workspace_bytes,
+                                         mmfd_stream_t stream) {
+  return beam_select_run("mmfd_beam_select_logprobs", true, B, nb, V, logprobs, ldl, running, out_score, out_beam,
+                         out_token, workspace, workspace_bytes, stream);
+}
+
+extern "C" int64_t mmfd_row_log_softmax_workspace_bytes(int64_t R, int64_t V) {
+  if (R < 1 || R > 65535 || V < 1 || V > (1 << 20)) {
+    mmfd_set_error(MMFD_ERR_INVALID, "mmfd_row_log_softmax_workspace_bytes: R = %lld (1 .. 65535), V = %lld (1 .. 2^20)",
+                   (long long)R, (long long)V);
+    return -1;
+  }
+  const int64_t slab = beam_slab(V), S = (V + slab - 1) / slab;
+  return R * S * 8;  // {max, sum} per (row, slab)
+}
+
+extern "C" int mmfd_row_log_softmax(int64_t R, int64_t V, float* logits, int64_t ldl, void* workspace,
+                                    int64_t workspace_bytes, mmfd_stream_t stream) {
+  MMFD_CHECK_ARG(R >= 1 && R <= 65535, "mmfd_row_log_softmax: R = %lld rows (1 .. 65535)", (long long)R);
+  MMFD_CHECK_ARG(V >= 1 && V <= (1 << 20), "mmfd_row_log_softmax: V = %lld (1 .. 2^20)", (long long)V);
+  MMFD_CHECK_ARG(logits, "mmfd_row_log_softmax: null pointer");
+  MMFD_CHECK_ARG(ldl >= V, "mmfd_row_log_softmax: leading dimension too small");
+  const int64_t need = mmfd_row_log_softmax_workspace_bytes(R, V);
+  MMFD_CHECK_ARG(workspace && workspace_bytes >= need && ((uintptr_t)workspace & 3) == 0,
+                 "mmfd_row_log_softmax: needs a 4-byte aligned workspace of %lld bytes "
+                 "(mmfd_row_log_softmax_workspace_bytes)", (long long)need);
+  const int slab = beam_slab(V);
+  const int64_t S = (V + slab - 1) / slab;
+  float* pm = (float*)workspace;  // [R][S]
+  float* ps = pm + R * S;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)S, (unsigned)R), block(BEAM_THREADS);
+  hipLaunchKernelGGL(beam_partial_kernel, grid, block, 0, s, logits, ldl, (int)V, slab, pm, ps);
+  MMFD_CHECK_LAUNCH("mmfd_row_log_softmax (partials)");
+  hipLaunchKernelGGL(beam_normalize_kernel, grid, block, 0, s, logits, ldl, (int)V, slab, pm, ps);
+  MMFD_CHECK_LAUNCH("mmfd_row_log_softmax (normalise)");
   return 0;
 }
 

@@ -224,6 +224,11 @@ SIGNATURES = {
     "mmfd_sample_select_resident_max": (_I64, []),
     "mmfd_sample_select_workspace_bytes": (_I64, [_I64, _I64]),
     "mmfd_sample_select": (_I, [_I64, _I64, _VP, _I64, _F, _I64, _F, _VP, _I64, _VP, _VP, _I64, _VP, _VP, _I64, _VP]),
+    "mmfd_row_log_softmax_workspace_bytes": (_I64, [_I64, _I64]),
+    "mmfd_row_log_softmax": (_I, [_I64, _I64, _VP, _I64, _VP, _I64, _VP]),
+    "mmfd_beam_select_logprobs": (_I, [_I64, _I64, _I64, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
+    "mmfd_logits_process": (_I, [_I64, _I64, _VP, _I64, _VP, _I64, _I64, _I, _I64, _F, _I64, _I, _I64, _VP, _I64, _VP]),
+    "mmfd_row_argmax": (_I, [_I64, _I64, _VP, _I64, _VP, _VP]),
     "mmfd_vocab_xent_fwd": (_I, [_I64, _I64, _VP, _I64, _VP, _F, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mmfd_vocab_xent_bwd": (_I, [_I, _I64, _I64, _VP, _I64, _VP, _VP, _VP, _F, _VP, _VP, _I64, _VP, _I64, _VP]),
 }
@@ -1575,11 +1580,12 @@ def _f32(t, shape, what):
         raise ValueError(f"{what} must be a contiguous fp32 tensor of shape {tuple(shape)}")
 
 
-def beam_select(logits, running, nb, *, out=None, workspace=None):
+def beam_select(logits, running, nb, *, out=None, workspace=None, logprobs=False):
     """per image the 2 nb best (score, beam, token) of its nb * V candidates, score = log_softmax(logits[row])
     + running[row]: logits fp32 [B * nb, V] (rows may be strided), running fp32 [B * nb]. Returns (score fp32,
     beam int32, token int32), each [B, 2 nb], best first; equal scores go to the lower beam, then the lower
-    token, and a NaN is never chosen over a number."""
+    token, and a NaN is never chosen over a number. logprobs: `logits` holds log-probabilities already
+    (row_log_softmax, then logits_process): score = logits[row] + running[row], no normalisation."""
     _require_cuda(logits, running, workspace)
     nb = int(nb)
     if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1 or nb < 1 or logits.shape[0] % nb:
@@ -1596,10 +1602,36 @@ def beam_select(logits, running, nb, *, out=None, workspace=None):
     _require_cuda(*out)
     if workspace is None:
         workspace = torch.empty(beam_select_workspace_bytes(B, nb, V), device=logits.device, dtype=torch.uint8)
-    _check(lib().mmfd_beam_select(B, nb, V, _ptr(logits), logits.stride(0), _ptr(running), _ptr(out[0]), _ptr(out[1]),
-                                  _ptr(out[2]), _ptr(workspace), workspace.numel() * workspace.element_size(),
-                                  _stream()), "mmfd_beam_select")
+    name = "mmfd_beam_select_logprobs" if logprobs else "mmfd_beam_select"
+    _check(getattr(lib(), name)(B, nb, V, _ptr(logits), logits.stride(0), _ptr(running), _ptr(out[0]), _ptr(out[1]),
+                                _ptr(out[2]), _ptr(workspace), workspace.numel() * workspace.element_size(),
+                                _stream()), name)
     return out
+
+
+def beam_select_logprobs(logprobs, running, nb, *, out=None, workspace=None):
+    """beam_select on log-probabilities (processed ones): score = logprobs[row] + running[row]"""
+    return beam_select(logprobs, running, nb, out=out, workspace=workspace, logprobs=True)
+
+
+def row_log_softmax_workspace_bytes(R, V):
+    n = lib().mmfd_row_log_softmax_workspace_bytes(int(R), int(V))
+    _check(0 if n > 0 else MMFD_ERR_INVALID, "mmfd_row_log_softmax_workspace_bytes")
+    return int(n)
+
+
+def row_log_softmax(logits, *, workspace=None):
+    """logits fp32 [R, V] (rows may be strided) <- logits - logsumexp(row), in place: what transformers' beam search
+    hands to the logits processors. The log-sum-exp is beam_select's."""
+    _require_cuda(logits, workspace)
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("row_log_softmax: logits must be an fp32 [R, V] view with a contiguous last dim")
+    R, V = logits.shape
+    if workspace is None:
+        workspace = torch.empty(row_log_softmax_workspace_bytes(R, V), device=logits.device, dtype=torch.uint8)
+    _check(lib().mmfd_row_log_softmax(R, V, _ptr(logits), logits.stride(0), _ptr(workspace),
+                                      workspace.numel() * workspace.element_size(), _stream()), "mmfd_row_log_softmax")
+    return logits
 
 
 def beam_update(cand, state, t, n_forced, last, eos, length_penalty, early_stopping, next_tokens):
@@ -1720,6 +1752,101 @@ def sample_select(logits, temperature, top_k, top_p, ctl, step, *, out=None, pro
                                     _ptr(probs), probs.stride(0) if probs is not None else 0, _ptr(kept),
                                     _ptr(workspace), workspace.numel() * workspace.element_size(), _stream()),
            "mmfd_sample_select")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# logits processors (csrc/logits.hip)
+# ------------------------------------------------------------------------------------------------
+MAX_SUPPRESS = 64      # ids in a suppress list (csrc/logits.hip LGT_MAX_SUPPRESS)
+MAX_HISTORY = 1024     # history positions a row may hold (LGT_MAX_LEN)
+
+
+def _int_arg(v, name, lo=0):
+    if isinstance(v, bool) or int(v) != v or v < lo:
+        raise ValueError(f"{name} must be an integer >= {lo}, got {v!r}")
+    return int(v)
+
+
+def check_processors(repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, min_new_tokens=0,
+                     suppress_tokens=None, vocab_size=None):
+    """the host-side refusal of processor arguments transformers' classes refuse too. Returns (penalty, ngram,
+    min_length, min_new_tokens, suppress) with suppress a tuple of ints (None -> ())."""
+    try:
+        p = float(repetition_penalty)
+    except (TypeError, ValueError):
+        p = float("nan")
+    if not (p > 0.0 and p != float("inf")):
+        raise ValueError(f"repetition_penalty must be a finite number > 0, got {repetition_penalty!r}")
+    n = _int_arg(no_repeat_ngram_size, "no_repeat_ngram_size")
+    ml = _int_arg(min_length, "min_length")
+    mn = _int_arg(min_new_tokens, "min_new_tokens")
+    if suppress_tokens is None:
+        sup = ()
+    else:
+        if isinstance(suppress_tokens, torch.Tensor):
+            suppress_tokens = suppress_tokens.reshape(-1).tolist()
+        sup = tuple(_int_arg(i, "suppress_tokens entries") for i in suppress_tokens)
+        if len(sup) > MAX_SUPPRESS:
+            raise ValueError(f"suppress_tokens holds {len(sup)} ids, at most {MAX_SUPPRESS} are supported")
+        if vocab_size is not None and any(i >= vocab_size for i in sup):
+            raise ValueError(f"suppress_tokens outside [0, {vocab_size})")
+    return p, n, ml, mn, sup
+
+
+def logits_process(scores, history, cur_len, *, repetition_penalty=1.0, no_repeat_ngram_size=0, suppress_eos=False,
+                   eos=0, suppress=None, n_suppress=None, history_layout="rows"):
+    """transformers' logits processors in place on scores fp32 [R, V] (rows may be strided), from each row's own
+    history (include/mmfd.h mmfd_logits_process): the repetition penalty on the scores as passed, then -inf into
+    the columns no_repeat_ngram_size bans, into `eos` when suppress_eos, and into the first n_suppress ids of the
+    device list `suppress` (int64, at most 64). history: int64 or int32, [R', >= cur_len] with
+    history_layout="rows" (row r, position i at history[r, i]) or [>= cur_len, R'] with "steps" (history[i, r]),
+    R' >= R, any strides. Greedy decoding and sampling pass the raw logits, beam search row_log_softmax's output."""
+    _require_cuda(scores, history, suppress)
+    if scores.dtype != torch.float32 or scores.dim() != 2 or scores.stride(1) != 1:
+        raise ValueError("logits_process: scores must be an fp32 [R, V] view with a contiguous last dim")
+    R, V = scores.shape
+    p, n, _, _, _ = check_processors(repetition_penalty, no_repeat_ngram_size)
+    cur_len = int(cur_len)
+    if history.dtype not in (torch.int64, torch.int32) or history.dim() != 2:
+        raise ValueError("logits_process: history must be a 2-D int64 or int32 tensor")
+    if history_layout not in ("rows", "steps"):
+        raise ValueError(f"logits_process: history_layout must be 'rows' or 'steps', got {history_layout!r}")
+    rdim, pdim = (0, 1) if history_layout == "rows" else (1, 0)
+    if not 1 <= cur_len <= min(history.shape[pdim], MAX_HISTORY) or history.shape[rdim] < R:
+        raise ValueError(f"logits_process: history {tuple(history.shape)} ({history_layout}) does not hold {R} rows of "
+                         f"cur_len = {cur_len} (1 .. {MAX_HISTORY}) ids")
+    if history.stride(rdim) < 0 or history.stride(pdim) < 1:
+        raise ValueError("logits_process: history strides must be positive")
+    if suppress is None:
+        n_sup = 0
+    else:
+        if suppress.dtype != torch.int64 or suppress.dim() != 1 or not suppress.is_contiguous():
+            raise ValueError("logits_process: suppress must be a contiguous int64 vector")
+        n_sup = suppress.numel() if n_suppress is None else int(n_suppress)
+        if not 0 <= n_sup <= min(suppress.numel(), MAX_SUPPRESS):
+            raise ValueError(f"logits_process: {n_sup} suppressed ids (at most {MAX_SUPPRESS}, and the list's length)")
+    if suppress_eos and not 0 <= int(eos) < V:
+        raise ValueError(f"logits_process: eos = {eos} outside [0, {V})")
+    _check(lib().mmfd_logits_process(R, V, _ptr(scores), scores.stride(0), _ptr(history), history.stride(rdim),
+                                     history.stride(pdim), history.element_size(), cur_len, p, n,
+                                     int(bool(suppress_eos)), int(eos), _ptr(suppress) if n_sup else None, n_sup,
+                                     _stream()), "mmfd_logits_process")
+    return scores
+
+
+def row_argmax(scores, *, out=None):
+    """argmax per row of scores fp32 [R, V] (rows may be strided): ties to the lowest index, a NaN never over a
+    number — lm_head_argmax's order, for scores edited after the LM head wrote them. Returns int64 [R]."""
+    _require_cuda(scores, out)
+    if scores.dtype != torch.float32 or scores.dim() != 2 or scores.stride(1) != 1:
+        raise ValueError("row_argmax: scores must be an fp32 [R, V] view with a contiguous last dim")
+    R, V = scores.shape
+    if out is None:
+        out = torch.empty(R, device=scores.device, dtype=torch.int64)
+    elif out.dtype != torch.int64 or tuple(out.shape) != (R,) or not out.is_contiguous():
+        raise ValueError(f"row_argmax: out must be a contiguous int64 tensor of shape ({R},)")
+    _check(lib().mmfd_row_argmax(R, V, _ptr(scores), scores.stride(0), _ptr(out), _stream()), "mmfd_row_argmax")
     return out
 
 

@@ -4,6 +4,7 @@ shapes, random weights and pixels) and the LM-head kernel alone.
   python tools/caption_bench.py [--batches 1 20] [--num-beams 1] [--reps 3] [--out FILE]
   python tools/caption_bench.py --loss [--batches 20] [--seq 21] [--reps 7] [--out FILE]
   python tools/caption_bench.py --sample [--top-k 50] [--top-p 0.9] [--temperature 1.0] [--num-return-sequences 1]
+  python tools/caption_bench.py --processors [--reps 7] [--out FILE]
 
 Per (batch, precision): wall time of `generate` (20 new tokens; host-synchronised, the ids copied back)
 eager and as one graph replay, and per precision the device time of kernels.lm_head_argmax at
@@ -18,7 +19,12 @@ vocabulary cross-entropy kernels on the model's [B * T, 30524] logits with the b
 --sample times `generate(do_sample=True, ...)` instead (batch * num_return_sequences decoder rows), eager and graph,
 with greedy decoding of as many rows in the same run as its yardstick, and `sample_step_times`: the device time of
 kernels.sample_select alone on [rows, 30524] logits for the call's filters and for each filter alone, beside
-kernels.beam_select at the same row count."""
+kernels.beam_select at the same row count.
+--processors times the logits processors (repetition_penalty 1.3, no_repeat_ngram_size 2, min_new_tokens 12 and three
+suppressed ids together): per precision, for greedy decoding, 3 beams and 3 samples per image, at batch 1 and at the
+largest batch the mode takes (32 decoder rows), the graph-replay wall time of `generate` with them off and on in
+the same run; and `processor_step_times`: the device time of kernels.logits_process, kernels.row_argmax and the
+beam path's kernels.row_log_softmax alone at V = 30524 on 1 and 32 rows of a 21-token history."""
 import argparse
 import json
 import os
@@ -183,6 +189,73 @@ def sample_main(a):
             f.write(line + "\n")
 
 
+PROCESSORS = dict(repetition_penalty=1.3, no_repeat_ngram_size=2, min_new_tokens=12, suppress_tokens=[100, 101, 103])
+
+
+def processor_step_times(R, V=30524, cur=21, reps=20):
+    """device time (us, median of reps, each between two events) of the kernels a step with processors adds, on
+    random N(0, 1) scores [R, V] and a random int64 step-major history of `cur` ids per row: the edits (all rules,
+    and the penalty alone), the row argmax of the greedy path, and the in-place log-softmax of the beam path beside
+    the selection with and without its own normalisation (3 beams per image when R is a multiple of 3, else 1)"""
+    dev = "cuda"
+    scores = torch.randn(R, V, device=dev)
+    hist = torch.randint(0, V, (cur, max(R, 16)), device=dev)
+    sup = torch.tensor(PROCESSORS["suppress_tokens"], dtype=torch.int64, device=dev)
+    tok = torch.zeros(R, dtype=torch.int64, device=dev)
+    out = {"rows": R, "V": V, "cur_len": cur, "argmax_bytes_per_row": V * 4}
+    out["edit_all_us"] = _device_us(lambda: K.logits_process(scores, hist, cur, repetition_penalty=1.3,
+                                                             no_repeat_ngram_size=2, suppress_eos=True, eos=102,
+                                                             suppress=sup, history_layout="steps"), reps)
+    scores = torch.randn(R, V, device=dev)
+    out["edit_penalty_us"] = _device_us(lambda: K.logits_process(scores, hist, cur, repetition_penalty=1.3,
+                                                                 history_layout="steps"), reps)
+    out["row_argmax_us"] = _device_us(lambda: K.row_argmax(scores, out=tok), reps)
+    nb = 3 if R % 3 == 0 else 1
+    running = -torch.rand(R, device=dev)
+    ws = torch.empty(K.beam_select_workspace_bytes(R // nb, nb, V), dtype=torch.uint8, device=dev)
+    cand = K.beam_select(scores, running, nb)
+    out["beam_select_us"] = _device_us(lambda: K.beam_select(scores, running, nb, out=cand, workspace=ws), reps)
+    out["beam_select_logprobs_us"] = _device_us(lambda: K.beam_select_logprobs(scores, running, nb, out=cand,
+                                                                                workspace=ws), reps)
+    out["row_log_softmax_us"] = _device_us(lambda: K.row_log_softmax(scores, workspace=ws), reps)
+    out["beam_select_num_beams"] = nb
+    return out
+
+
+def processors_main(a):
+    torch.manual_seed(0)
+    m = BlipForConditionalGeneration().to("cuda").eval()
+    for p in m.parameters():
+        p.requires_grad_(False)
+    modes = {"greedy": (dict(), 1, [1, 32]), "beams3": (dict(num_beams=3), 3, [1, 10]),
+             "samples3": (dict(do_sample=True, top_k=50, top_p=0.9, num_return_sequences=3, seed=1), 3, [1, 10])}
+    res = {"generate": [], "processor_step_times": [], "processors": PROCESSORS}
+    for prec in ("fp32", "bf16"):
+        m.set_precision(prec)
+        for name, (kw, per_image, batches) in modes.items():
+            for B in batches:
+                px = torch.randn(B, 3, 384, 384, device="cuda")
+                row = {"precision": prec, "mode": name, "B": B, "rows": B * per_image}
+                for tag, proc in (("off", {}), ("on", PROCESSORS)):
+                    t_min, t_med = wall(lambda: m.generate(px, use_graph=True, **kw, **proc), a.reps)
+                    row[tag + "_ms"], row[tag + "_ms_min"] = round(t_med, 2), round(t_min, 2)
+                    row[tag + "_ms_per_image"] = round(t_med / B, 3)
+                    row[tag + "_tokens"] = int(m.generate(px, use_graph=True, **kw, **proc).shape[1]) - 1
+                row["on_minus_off_us_per_step"] = round((row["on_ms"] - row["off_ms"]) * 1e3 / 20, 1)
+                res["generate"].append(row)
+                print(row, file=sys.stderr, flush=True)
+            m.invalidate_caches()
+    for R in (1, 32, 30):
+        res["processor_step_times"].append(processor_step_times(R))
+        print(res["processor_step_times"][-1], file=sys.stderr, flush=True)
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def xent_times(dt, R, V=30524, reps=20):
     """device time (us, median) of vocab_xent_fwd (both launches) and vocab_xent_bwd on random [R, V] logits, laid
     out as the model lays them out: rows of vocab_ld(V) columns"""
@@ -272,7 +345,11 @@ def main():
     ap.add_argument("--top-p", type=float, default=0.9)
     ap.add_argument("--temperature", type=float, default=1.0)
     ap.add_argument("--num-return-sequences", type=int, default=1)
+    ap.add_argument("--processors", action="store_true", help="time generate with the logits processors off and on")
     a = ap.parse_args()
+    if a.processors:
+        a.reps = max(a.reps, 7)
+        return processors_main(a)
     if a.sample:
         return sample_main(a)
     if a.loss:
