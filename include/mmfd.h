@@ -529,6 +529,16 @@ int64_t mmfd_lm_head_argmax_slab(int dtype, int64_t B, int64_t V, int64_t K);
 int mmfd_lm_head_argmax(int dtype, int64_t B, int64_t V, int64_t K, const void* x, int64_t ldx, const void* W,
                         int64_t ldw, const float* bias, int64_t* out_idx, float* logits, int64_t ldl,
                         void* workspace, int64_t workspace_bytes, mmfd_stream_t stream);
+/* The same for 1 <= B <= 256 rows: the rows go through the kernel above in tiles of 32 (one launch over
+   vocabulary slabs x row tiles, the last tile padded with zero rows, then the same reduce), so the logit of row r
+   is bit for bit what mmfd_lm_head_argmax writes for the 32-row block that holds r, and a row's token never
+   depends on how many other rows share the call. W is read once per row tile. Arguments, tie and NaN rules,
+   the optional logits and the workspace (mmfd_lm_head_argmax_wide_workspace_bytes) as above; K <= 1024 elements
+   in either dtype (a 32-row tile of x lies in LDS as fp32: what the kernel above takes at 32 rows). */
+int64_t mmfd_lm_head_argmax_wide_workspace_bytes(int dtype, int64_t B, int64_t V, int64_t K);
+int mmfd_lm_head_argmax_wide(int dtype, int64_t B, int64_t V, int64_t K, const void* x, int64_t ldx, const void* W,
+                             int64_t ldw, const float* bias, int64_t* out_idx, float* logits, int64_t ldl,
+                             void* workspace, int64_t workspace_bytes, mmfd_stream_t stream);
 /* The greedy rule of one step, per row b: tok = forced[b*forced_ld] when forced != NULL (a prompt or
    teacher forcing), else pad when finished[b] was set before this step, else argmax[b];
    next[b*next_ld] = tok; finished[b] |= (tok == eos). finished: int32 [B]. */

@@ -150,6 +150,10 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
     text_decoder.cls.predictions.*; the decoder weight and bias are the word embeddings and
     cls.predictions.bias). `generate` returns the token ids transformers' greedy `generate` returns."""
 
+    # rows of one greedy generate call. kernels.lm_head_argmax_wide takes 256; a 256-row call of the default model
+    # did not complete on an MI355X and the cause is not known (DESIGN.md, "Captioning"), 128 rows is what ran
+    MAX_GREEDY_ROWS = 128
+
     def __init__(self, config: BlipConfig | None = None, **kw):
         super().__init__()
         c = self.config = config or BlipConfig(**kw)
@@ -319,13 +323,18 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
                          eos=self.config.text.sep_token_id, suppress=st["suppress"] if sup else None,
                          n_suppress=len(sup), history_layout=layout)
 
-    def _state(self, B, steps, dev, proc=None):
+    def _state(self, B, steps, dev, proc=None, wide_ok=False):
         """the device buffers of one (batch, steps, precision): static inputs, caches, workspaces; with logits
-        processors also the fp32 logits of one step and the suppress list"""
+        processors also the fp32 logits of one step and the suppress list. wide_ok (greedy generate): more than 32
+        rows get the wide LM head's workspace; such a state is large (its graph holds the cross-attention K|V of
+        every row), so the cached states and their graphs go before its buffers are allocated"""
         key = (B, steps, self.compute_dtype, str(dev)) + self._proc_key(proc)
         st = self._states.get(key)
         if st is not None:
             return st
+        wide = bool(wide_ok) and B > 32
+        if wide:
+            self._states.clear()
         vc, tc = self.config.vision, self.config.text
         dt, E, H = self.compute_dtype, tc.hidden_size, tc.num_attention_heads
         Li = (vc.image_size // vc.patch_size) ** 2 + 1
@@ -347,10 +356,17 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
         need = max(K.lib().mmfd_attn_decode_workspace_bytes(B, H, E // H, Li),
                    K.lib().mmfd_attn_decode_workspace_bytes(Bp, H, E // H, steps), 16)
         st["attn_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
-        need = K.lib().mmfd_lm_head_argmax_workspace_bytes(K.dtype_code(dt), B, tc.vocab_size, E)
-        if need <= 0:
-            raise ValueError(f"mmfd BLIP: the LM head kernel takes at most 32 rows and widths up to 1024 (fp32) / 2048 "
-                             f"(bf16), got batch {B}, width {E}")
+        st["wide"] = wide
+        if wide:
+            need = K.lib().mmfd_lm_head_argmax_wide_workspace_bytes(K.dtype_code(dt), B, tc.vocab_size, E)
+            if need <= 0:
+                raise ValueError(f"mmfd BLIP: the wide LM head kernel takes at most 256 rows and widths up to 1024, "
+                                 f"got batch {B}, width {E}")
+        else:
+            need = K.lib().mmfd_lm_head_argmax_workspace_bytes(K.dtype_code(dt), B, tc.vocab_size, E)
+            if need <= 0:
+                raise ValueError(f"mmfd BLIP: the LM head kernel takes at most 32 rows and widths up to 1024 (fp32) / "
+                                 f"2048 (bf16), got batch {B}, width {E}")
         st["lm_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
         self._proc_buffers(st, proc, B, dev)
         if len(self._states) >= 8:
@@ -439,15 +455,15 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
         tc = self.config.text
         B, P = st["B"], sc.P
         g = self._hidden(sc, st, cross, t, st["self_kv"])
+        # more than 32 rows (greedy generate only): the wide LM head, the narrow kernel's body over 32-row tiles
+        lm_head = K.lm_head_argmax_wide if st.get("wide") else K.lm_head_argmax
         if st.get("proc") is None or logits is not None:
-            K.lm_head_argmax(g[:B], sc.w(WORD), P[HEAD + "bias"], out=st["argmax"], logits=logits,
-                             workspace=st["lm_ws"])
+            lm_head(g[:B], sc.w(WORD), P[HEAD + "bias"], out=st["argmax"], logits=logits, workspace=st["lm_ws"])
         elif not forced:
             # logits processors: the LM head stores its fp32 logits, the edits run on them, and the argmax is taken
             # of the edited row (a fix-up of the fused argmax would not do: were the raw winner an edited column,
             # the best unedited one would be unknown). A forced step needs neither: its token is the prompt's.
-            K.lm_head_argmax(g[:B], sc.w(WORD), P[HEAD + "bias"], out=st["argmax"], logits=st["logits"],
-                             workspace=st["lm_ws"])
+            lm_head(g[:B], sc.w(WORD), P[HEAD + "bias"], out=st["argmax"], logits=st["logits"], workspace=st["lm_ws"])
             self._edit(st, st["logits"], st["seq"], "steps", t)
             K.row_argmax(st["logits"], out=st["argmax"])
         if select:
@@ -493,6 +509,13 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
         `input_ids`: an optional prompt shared by all rows, fed one token per step in place of the argmax.
         use_graph: replay one captured HIP graph of all steps and trim on the host; else run eagerly and
         stop once every row has finished.
+        Greedy decoding takes up to 128 rows per call (MAX_GREEDY_ROWS): up to 32 on kernels.lm_head_argmax, 33 ..
+        128 on kernels.lm_head_argmax_wide, whose logits are bit for bit those of the narrow kernel on the row's
+        32-row block, so the LM head never makes a caption depend on how many images share the call. (The kernel
+        takes 256 rows; `generate` stops at 128 because a 256-row call of the default model did not complete on an
+        MI355X and the cause is not known: DESIGN.md, "Captioning".) A state of more than 32 rows is large (5.4 GB
+        of cross-attention K|V at 128 rows in fp32): creating one drops the other cached states and their graphs
+        first. Beam search, sampling and forward_logits keep 32 rows.
         num_beams in 2 .. 8 (num_beams * batch <= 32, the LM head's rows): transformers' beam search with
         `length_penalty` and `early_stopping` (False or True), no sampling, one returned sequence per image — the
         array `generate(pixel_values, input_ids, num_beams=..., length_penalty=..., early_stopping=...,
@@ -556,12 +579,14 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
         if num_beams > 1:
             return self._generate_beams(sc, dev, px, prompt, int(max_new_tokens), bool(use_graph), int(num_beams),
                                         float(length_penalty), bool(early_stopping), proc)
+        if B > self.MAX_GREEDY_ROWS:
+            raise ValueError(f"greedy decoding takes at most {self.MAX_GREEDY_ROWS} rows per call, got batch {B}")
         n_forced = len(prompt) - 1
         steps = n_forced + int(max_new_tokens)
         if steps < 1 or steps + 1 > tc.max_position_embeddings:
             raise ValueError(f"prompt ({len(prompt)}) + max_new_tokens ({max_new_tokens}) must lie in "
                              f"[2, {tc.max_position_embeddings}]")
-        st = self._state(B, steps, dev, proc)
+        st = self._state(B, steps, dev, proc, wide_ok=True)
         if tuple(px.shape) != tuple(st["px"].shape):
             raise ValueError(f"pixel_values must be {tuple(st['px'].shape)}, got {tuple(px.shape)}")
         st["px"].copy_(px)

@@ -10,6 +10,7 @@
 //   mmfd_lm_head_argmax  argmax_v (x . W[v] + bias[v]) for B <= 32 rows without the [B, V] logits ever
 //                        being written: each workgroup streams one slab of vocabulary rows once for all B
 //                        rows and leaves one (max, index) per row; a second kernel reduces those.
+//                        mmfd_lm_head_argmax_wide: up to 256 rows, a grid of slabs x 32-row tiles of the same body.
 //   mmfd_greedy_select   the greedy rule per row (forced token, pad after eos, finished flag).
 //
 // Nothing here hands data between workgroups inside a launch: every phase is its own kernel on the stream.
@@ -222,12 +223,14 @@ bool lmh_plan(int dtype, int64_t B, int64_t V, int64_t K, LmhPlan& pl) {
 
 __device__ __forceinline__ bool lmh_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 
+// One workgroup's share: slab blockIdx.x of the vocabulary against the B <= BT rows of x. The (max, index) of row
+// b goes to pval / pidx[blockIdx.x * pld + b]. Both kernels below are this body: the logit of a row is the same
+// bits whichever of them computed it.
 template <typename T, int BT, int NJ>
-__global__ __launch_bounds__(64 * LMH_WAVES) void lm_head_kernel(const T* __restrict__ x, int64_t ldx,
-                                                                  const T* __restrict__ W, int64_t ldw,
-                                                                  const float* __restrict__ bias, int B, int V, int K,
-                                                                  int slab, float* __restrict__ logits, int64_t ldl,
-                                                                  float* __restrict__ pval, int* __restrict__ pidx) {
+__device__ __forceinline__ void lm_head_tile(const T* __restrict__ x, int64_t ldx, const T* __restrict__ W, int64_t ldw,
+                                             const float* __restrict__ bias, int B, int V, int K, int slab,
+                                             float* __restrict__ logits, int64_t ldl, float* __restrict__ pval,
+                                             int* __restrict__ pidx, int64_t pld) {
   constexpr int E = Chunk<T>::E, Q = E / 4, R = lmh_rows(E, BT, NJ), N = BT * R;
   static_assert(N <= 64, "one (row, batch) sum per lane after the reduce");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -307,9 +310,34 @@ __global__ __launch_bounds__(64 * LMH_WAVES) void lm_head_kernel(const T* __rest
         const int i = sidx[wv][r * BT + threadIdx.x];
         if (lmh_better(v, i, bv, bi)) { bv = v; bi = i; }
       }
-    pval[(int64_t)blockIdx.x * B + threadIdx.x] = bv;
-    pidx[(int64_t)blockIdx.x * B + threadIdx.x] = bi;
+    pval[(int64_t)blockIdx.x * pld + threadIdx.x] = bv;
+    pidx[(int64_t)blockIdx.x * pld + threadIdx.x] = bi;
   }
+}
+
+template <typename T, int BT, int NJ>
+__global__ __launch_bounds__(64 * LMH_WAVES) void lm_head_kernel(const T* __restrict__ x, int64_t ldx,
+                                                                  const T* __restrict__ W, int64_t ldw,
+                                                                  const float* __restrict__ bias, int B, int V, int K,
+                                                                  int slab, float* __restrict__ logits, int64_t ldl,
+                                                                  float* __restrict__ pval, int* __restrict__ pidx) {
+  lm_head_tile<T, BT, NJ>(x, ldx, W, ldw, bias, B, V, K, slab, logits, ldl, pval, pidx, B);
+}
+
+// B <= 256 rows in tiles of LMH_TILE: workgroup (g, t) is lm_head_tile on slab g and rows 32 t .. 32 t + 31 (the
+// last tile zero padded, as the narrow kernel pads a short batch), so W is read once per row tile; the partials
+// lie [G][B] as the narrow kernel leaves them and lm_head_final_kernel reduces them unchanged.
+constexpr int LMH_TILE = 32, LMH_WIDE_ROWS = 256;
+template <typename T, int NJ>
+__global__ __launch_bounds__(64 * LMH_WAVES) void lm_head_wide_kernel(const T* __restrict__ x, int64_t ldx,
+                                                                       const T* __restrict__ W, int64_t ldw,
+                                                                       const float* __restrict__ bias, int B, int V,
+                                                                       int K, int slab, float* __restrict__ logits,
+                                                                       int64_t ldl, float* __restrict__ pval,
+                                                                       int* __restrict__ pidx) {
+  const int b0 = blockIdx.y * LMH_TILE;
+  lm_head_tile<T, LMH_TILE, NJ>(x + b0 * ldx, ldx, W, ldw, bias, min(LMH_TILE, B - b0), V, K, slab,
+                                logits ? logits + b0 * ldl : nullptr, ldl, pval + b0, pidx + b0, B);
 }
 
 // one wave per batch row over the G per-workgroup partials: the largest value, ties to the lowest index; a
@@ -367,6 +395,43 @@ int lmh_launch_bt(const LmhPlan& pl, const void* x, int64_t ldx, const void* W, 
     case 16: return lmh_launch_nj<T, 16>(pl, x, ldx, W, ldw, bias, B, V, K, logits, ldl, pval, pidx, s);
     default: return lmh_launch_nj<T, 32>(pl, x, ldx, W, ldw, bias, B, V, K, logits, ldl, pval, pidx, s);
   }
+}
+
+template <typename T, int NJ>
+int lmh_wide_launch(const LmhPlan& pl, const void* x, int64_t ldx, const void* W, int64_t ldw, const float* bias,
+                    int64_t B, int64_t V, int64_t K, float* logits, int64_t ldl, float* pval, int* pidx, hipStream_t s) {
+  auto kern = &lm_head_wide_kernel<T, NJ>;
+  if (pl.lds > 48 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)pl.lds) != hipSuccess)
+    return mmfd_set_error(MMFD_ERR_UNSUPPORTED, "mmfd_lm_head_argmax_wide: cannot reserve %lld bytes of LDS",
+                          (long long)pl.lds);
+  const dim3 grid((unsigned)pl.G, (unsigned)((B + LMH_TILE - 1) / LMH_TILE));
+  hipLaunchKernelGGL(kern, grid, dim3(64 * LMH_WAVES), (size_t)pl.lds, s, (const T*)x, ldx, (const T*)W, ldw, bias,
+                     (int)B, (int)V, (int)K, pl.slab, logits, ldl, pval, pidx);
+  return 0;
+}
+
+template <typename T>
+int lmh_wide_launch_nj(const LmhPlan& pl, const void* x, int64_t ldx, const void* W, int64_t ldw, const float* bias,
+                       int64_t B, int64_t V, int64_t K, float* logits, int64_t ldl, float* pval, int* pidx,
+                       hipStream_t s) {
+  switch (pl.NJ) {
+    case 1: return lmh_wide_launch<T, 1>(pl, x, ldx, W, ldw, bias, B, V, K, logits, ldl, pval, pidx, s);
+    case 2: return lmh_wide_launch<T, 2>(pl, x, ldx, W, ldw, bias, B, V, K, logits, ldl, pval, pidx, s);
+    case 3: return lmh_wide_launch<T, 3>(pl, x, ldx, W, ldw, bias, B, V, K, logits, ldl, pval, pidx, s);
+    default: return lmh_wide_launch<T, 4>(pl, x, ldx, W, ldw, bias, B, V, K, logits, ldl, pval, pidx, s);
+  }
+}
+
+// the wide kernel's plan is the narrow kernel's at a full row tile: the same slabs, so the same workgroup
+// computes a vocabulary row however many rows the call holds
+// (a tile of x lies in LDS as fp32, 64 lanes x 16 bytes per chunk: beside the 4 KiB of per-wave partials that is
+// within the 160 KiB of a workgroup up to 1024 elements per row in either dtype, as at 32 rows of the narrow kernel)
+constexpr int64_t LMH_WIDE_MAX_K = 1024;
+bool lmh_wide_plan(int dtype, int64_t B, int64_t V, int64_t K, LmhPlan& pl) {
+  return B >= 1 && B <= LMH_WIDE_ROWS && K <= LMH_WIDE_MAX_K && lmh_plan(dtype, LMH_TILE, V, K, pl) &&
+         pl.lds + 4096 <= 160 * 1024;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -527,6 +592,47 @@ extern "C" int mmfd_lm_head_argmax(int dtype, int64_t B, int64_t V, int64_t K, c
   MMFD_CHECK_LAUNCH("mmfd_lm_head_argmax");
   hipLaunchKernelGGL(lm_head_final_kernel, dim3((unsigned)B), dim3(64), 0, s, pval, pidx, pl.G, (int)B, out_idx);
   MMFD_CHECK_LAUNCH("mmfd_lm_head_argmax (final)");
+  return 0;
+}
+
+extern "C" int64_t mmfd_lm_head_argmax_wide_workspace_bytes(int dtype, int64_t B, int64_t V, int64_t K) {
+  LmhPlan pl;
+  if ((dtype != MMFD_F32 && dtype != MMFD_BF16) || !lmh_wide_plan(dtype, B, V, K, pl)) {
+    mmfd_set_error(MMFD_ERR_INVALID, "mmfd_lm_head_argmax_wide_workspace_bytes: unsupported shape");
+    return -1;
+  }
+  return (int64_t)pl.G * B * 8;
+}
+
+extern "C" int mmfd_lm_head_argmax_wide(int dtype, int64_t B, int64_t V, int64_t K, const void* x, int64_t ldx,
+                                        const void* W, int64_t ldw, const float* bias, int64_t* out_idx, float* logits,
+                                        int64_t ldl, void* workspace, int64_t workspace_bytes, mmfd_stream_t stream) {
+  MMFD_CHECK_ARG(dtype == MMFD_F32 || dtype == MMFD_BF16, "mmfd_lm_head_argmax_wide: bad dtype");
+  MMFD_CHECK_ARG(B >= 1 && B <= LMH_WIDE_ROWS, "mmfd_lm_head_argmax_wide: B = %lld (1 .. %d rows)", (long long)B,
+                 LMH_WIDE_ROWS);
+  MMFD_CHECK_ARG(V >= 1 && V < (1 << 30), "mmfd_lm_head_argmax_wide: V = %lld", (long long)V);
+  const int64_t epc = dtype == MMFD_BF16 ? 8 : 4;
+  LmhPlan pl;
+  MMFD_CHECK_ARG(lmh_wide_plan(dtype, B, V, K, pl),
+                 "mmfd_lm_head_argmax_wide: K = %lld must be a multiple of %lld and <= %lld (a 32-row tile of x lies "
+                 "in LDS as fp32)", (long long)K, (long long)epc, (long long)LMH_WIDE_MAX_K);
+  MMFD_CHECK_ARG(x && W && out_idx, "mmfd_lm_head_argmax_wide: null pointer");
+  MMFD_CHECK_ARG(ldx >= K && ldw >= K && (!logits || ldl >= V), "mmfd_lm_head_argmax_wide: leading dimension too small");
+  MMFD_CHECK_ARG(((uintptr_t)W & 15) == 0 && ldw % epc == 0, "mmfd_lm_head_argmax_wide: W rows must be 16-byte aligned");
+  const int64_t need = (int64_t)pl.G * B * 8;
+  MMFD_CHECK_ARG(workspace && workspace_bytes >= need && ((uintptr_t)workspace & 3) == 0,
+                 "mmfd_lm_head_argmax_wide: needs a workspace of %lld bytes (mmfd_lm_head_argmax_wide_workspace_bytes)",
+                 (long long)need);
+  float* pval = (float*)workspace;
+  int* pidx = (int*)(pval + (int64_t)pl.G * B);
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = dtype == MMFD_F32
+                     ? lmh_wide_launch_nj<float>(pl, x, ldx, W, ldw, bias, B, V, K, logits, ldl, pval, pidx, s)
+                     : lmh_wide_launch_nj<bf16>(pl, x, ldx, W, ldw, bias, B, V, K, logits, ldl, pval, pidx, s);
+  if (rc) return rc;
+  MMFD_CHECK_LAUNCH("mmfd_lm_head_argmax_wide");
+  hipLaunchKernelGGL(lm_head_final_kernel, dim3((unsigned)B), dim3(64), 0, s, pval, pidx, pl.G, (int)B, out_idx);
+  MMFD_CHECK_LAUNCH("mmfd_lm_head_argmax_wide (final)");
   return 0;
 }
 

@@ -215,6 +215,8 @@ SIGNATURES = {
     "mmfd_lm_head_argmax_workspace_bytes": (_I64, [_I, _I64, _I64, _I64]),
     "mmfd_lm_head_argmax_slab": (_I64, [_I, _I64, _I64, _I64]),
     "mmfd_lm_head_argmax": (_I, [_I, _I64, _I64, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _VP, _I64, _VP, _I64, _VP]),
+    "mmfd_lm_head_argmax_wide_workspace_bytes": (_I64, [_I, _I64, _I64, _I64]),
+    "mmfd_lm_head_argmax_wide": (_I, [_I, _I64, _I64, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _VP, _I64, _VP, _I64, _VP]),
     "mmfd_greedy_select": (_I, [_I64, _VP, _VP, _I64, _VP, _I64, _I64, _VP, _I64, _VP]),
     "mmfd_beam_select_slab": (_I64, [_I64]),
     "mmfd_beam_select_workspace_bytes": (_I64, [_I64, _I64, _I64]),
@@ -1532,6 +1534,44 @@ def lm_head_argmax(x, W, bias=None, *, out=None, logits=None, workspace=None):
     _check(lib().mmfd_lm_head_argmax(code, B, V, Kd, _ptr(x), _ld(x), _ptr(W), _ld(W), _ptr(bias), _ptr(out),
                                      _ptr(logits), _ld(logits) if logits is not None else 0, _ptr(workspace),
                                      workspace.numel() * workspace.element_size(), _stream()), "mmfd_lm_head_argmax")
+    return out
+
+
+def lm_head_wide_workspace_bytes(dtype, B, V, K):
+    """bytes of workspace lm_head_argmax_wide needs for these shapes"""
+    need = lib().mmfd_lm_head_argmax_wide_workspace_bytes(dtype_code(dtype), int(B), int(V), int(K))
+    _check(0 if need > 0 else MMFD_ERR_INVALID, "mmfd_lm_head_argmax_wide_workspace_bytes")
+    return int(need)
+
+
+def lm_head_argmax_wide(x, W, bias=None, *, out=None, logits=None, workspace=None):
+    """lm_head_argmax for 1 <= B <= 256 rows: 32-row tiles through the same kernel body in one launch, every logit
+    bit for bit what lm_head_argmax gives for the row's 32-row block (a short last block zero padded). A
+    `workspace` that is given must hold lm_head_wide_workspace_bytes (it is never replaced here)."""
+    _require_cuda(x, W, bias, out, logits, workspace)
+    if x.dtype != W.dtype:
+        raise TypeError(f"lm_head_argmax_wide operands must share a dtype ({x.dtype} vs {W.dtype})")
+    B, Kd = x.shape
+    V = W.shape[0]
+    if W.shape[1] != Kd:
+        raise ValueError(f"lm_head_argmax_wide inner dims differ: {Kd} vs {W.shape[1]}")
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != V or not bias.is_contiguous()):
+        raise ValueError("bias must be a contiguous fp32 vector of length V")
+    if logits is not None and (logits.dtype != torch.float32 or tuple(logits.shape) != (B, V)):
+        raise ValueError("logits must be an fp32 [B, V] view")
+    if out is None:
+        out = torch.empty(B, device=x.device, dtype=torch.int64)
+    elif out.dtype != torch.int64 or out.numel() != B or not out.is_contiguous():
+        raise ValueError("out must be a contiguous int64 vector of length B")
+    code = dtype_code(x.dtype)
+    if workspace is None:
+        need = lib().mmfd_lm_head_argmax_wide_workspace_bytes(code, B, V, Kd)
+        _check(0 if need > 0 else MMFD_ERR_INVALID, "mmfd_lm_head_argmax_wide")
+        workspace = torch.empty(need, device=x.device, dtype=torch.uint8)
+    _check(lib().mmfd_lm_head_argmax_wide(code, B, V, Kd, _ptr(x), _ld(x), _ptr(W), _ld(W), _ptr(bias), _ptr(out),
+                                          _ptr(logits), _ld(logits) if logits is not None else 0, _ptr(workspace),
+                                          workspace.numel() * workspace.element_size(), _stream()),
+           "mmfd_lm_head_argmax_wide")
     return out
 
 

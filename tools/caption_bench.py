@@ -5,6 +5,8 @@ shapes, random weights and pixels) and the LM-head kernel alone.
   python tools/caption_bench.py --loss [--batches 20] [--seq 21] [--reps 7] [--out FILE]
   python tools/caption_bench.py --sample [--top-k 50] [--top-p 0.9] [--temperature 1.0] [--num-return-sequences 1]
   python tools/caption_bench.py --processors [--reps 7] [--out FILE]
+  python tools/caption_bench.py --lm-head-wide [--out FILE]
+  python tools/caption_bench.py --csv 512 [--batch-rows 64] [--csv-side 400] [--out FILE]
 
 Per (batch, precision): wall time of `generate` (20 new tokens; host-synchronised, the ids copied back)
 eager and as one graph replay, and per precision the device time of kernels.lm_head_argmax at
@@ -24,7 +26,12 @@ kernels.beam_select at the same row count.
 suppressed ids together): per precision, for greedy decoding, 3 beams and 3 samples per image, at batch 1 and at the
 largest batch the mode takes (32 decoder rows), the graph-replay wall time of `generate` with them off and on in
 the same run; and `processor_step_times`: the device time of kernels.logits_process, kernels.row_argmax and the
-beam path's kernels.row_log_softmax alone at V = 30524 on 1 and 32 rows of a 21-token history."""
+beam path's kernels.row_log_softmax alone at V = 30524 on 1 and 32 rows of a 21-token history.
+--batches takes greedy batches up to 128 (above 32 rows `generate` and the LM-head probe run on
+kernels.lm_head_argmax_wide). --lm-head-wide times the LM head alone: the narrow kernel at 32 rows, the wide one at
+32, 64, 128 and 256, warm and cold. --csv N writes N synthetic JPEGs and a CSV of N / 2 rows to a temporary directory
+and times mmfd.caption.process_csv end to end (images/s, JPEG decode included) beside the same files decoded in this
+process and captioned in 32-row chunks, the decode pool alone and the GPU alone."""
 import argparse
 import json
 import os
@@ -51,26 +58,30 @@ def wall(fn, reps):
     return min(ts) * 1e3, sorted(ts)[len(ts) // 2] * 1e3
 
 
-def lm_head_rate(dtype, B, V=30524, Kd=768, reps=20):
+def lm_head_rate(dtype, B, V=30524, Kd=768, reps=20, wide=None):
+    """wide: time kernels.lm_head_argmax_wide (default: whenever B > 32, the rows the narrow kernel refuses)"""
+    wide = B > 32 if wide is None else wide
+    head = K.lm_head_argmax_wide if wide else K.lm_head_argmax
     x = torch.randn(B, Kd, device="cuda").to(dtype)
     W = (torch.randn(V, Kd, device="cuda") * 0.02).to(dtype)
     bias = torch.zeros(V, device="cuda")
     flush = torch.empty(512 << 20, dtype=torch.uint8, device="cuda")  # larger than the 256 MiB last-level cache
     out = torch.empty(B, dtype=torch.int64, device="cuda")
-    K.lm_head_argmax(x, W, bias, out=out)
+    head(x, W, bias, out=out)
     cold, warm = [], []
     for i in range(reps):
         if i % 2 == 0:
             flush.zero_()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        K.lm_head_argmax(x, W, bias, out=out)
+        head(x, W, bias, out=out)
         e1.record()
         torch.cuda.synchronize()
         (cold if i % 2 == 0 else warm).append(e0.elapsed_time(e1) * 1e-3)
     nbytes = W.numel() * W.element_size() + bias.numel() * 4 + x.numel() * x.element_size()
     med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
-    return {"B": B, "bytes": nbytes, "us_cold": round(med(cold) * 1e6, 1), "us_warm": round(med(warm) * 1e6, 1),
+    return {"B": B, "kernel": "wide" if wide else "narrow", "row_tiles": (B + 31) // 32 if wide else 1,
+            "bytes": nbytes, "us_cold": round(med(cold) * 1e6, 1), "us_warm": round(med(warm) * 1e6, 1),
             "TBps_cold": round(nbytes / med(cold) / 1e12, 3), "TBps_warm": round(nbytes / med(warm) / 1e12, 3),
             "note": "both launches (partials + final reduce) between the events; cold = after a 512 MiB fill"}
 
@@ -187,6 +198,105 @@ def sample_main(a):
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             f.write(line + "\n")
+
+
+def wide_head_main(a):
+    """the LM head alone at the model's shapes: the narrow kernel at 32 rows, the wide one at 32 .. 256"""
+    res = {"lm_head": []}
+    for prec, dt in (("fp32", torch.float32), ("bf16", torch.bfloat16)):
+        for B, wide in ((32, False), (32, True), (64, True), (128, True), (256, True)):
+            res["lm_head"].append(dict(lm_head_rate(dt, B, wide=wide), precision=prec))
+            print(res["lm_head"][-1], file=sys.stderr, flush=True)
+    _emit(res, a)
+
+
+def _emit(res, a):
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+class IdTokenizer:
+    """stands in for a tokenizer (none is needed to time the driver): a caption is its ids in decimal"""
+
+    def batch_decode(self, ids, skip_special_tokens=True):
+        return [" ".join(str(i) for i in row) for row in ids]
+
+
+def csv_main(a):
+    """the driver end to end on a.csv synthetic JPEGs (a.csv // 2 rows): images/s of mmfd.caption.process_csv, JPEG
+    decode included, beside the same files decoded in this process and captioned by Captioner.caption in 32-row
+    chunks (what a driver on the 32-row model would do), the decode pool alone and the GPU alone"""
+    import tempfile
+
+    import numpy as np
+    import pandas as pd
+    from PIL import Image
+
+    from mmfd.caption import Captioner, process_csv
+    from mmfd.hostdecode import DecodePool
+    n = a.csv // 2 * 2
+    rng = np.random.default_rng(0)
+    torch.manual_seed(0)
+    m = BlipForConditionalGeneration().to("cuda").eval()
+    for p in m.parameters():
+        p.requires_grad_(False)
+    res = {"csv": [], "images": n, "image_size": [a.csv_side, a.csv_side], "batch_rows": a.batch_rows}
+    with tempfile.TemporaryDirectory() as root:
+        os.makedirs(os.path.join(root, "img"))
+        low = rng.integers(0, 256, (n, a.csv_side // 8, a.csv_side // 8, 3), dtype=np.uint8)
+        for i in range(n):  # smooth noise: JPEGs of a photograph's size on disk rather than of white noise's
+            Image.fromarray(low[i]).resize((a.csv_side, a.csv_side), Image.BICUBIC).save(
+                os.path.join(root, "img", f"{i}.jpg"), quality=90)
+        rows = [{"claim": f"c{r}", "evidence": f"e{r}", "claim_image": f"img/{2 * r}.jpg",
+                 "evidence_image": f"img/{2 * r + 1}.jpg"} for r in range(n // 2)]
+        src = os.path.join(root, "in.csv")
+        pd.DataFrame(rows).to_csv(src, index=False)
+        paths = [os.path.join(root, "img", f"{i}.jpg") for i in range(n)]
+        for prec in ("fp32", "bf16"):
+            m.set_precision(prec)
+            row = {"precision": prec}
+            wide = Captioner(m, tokenizer=IdTokenizer(), max_rows=max(32, 2 * a.batch_rows))
+            warm = os.path.join(root, "warm.csv")
+            process_csv(src, warm, wide, root=root, batch_rows=a.batch_rows, max_batches=1)  # captures the graph
+            dst = os.path.join(root, f"out_{prec}.csv")
+            t0 = time.perf_counter()
+            process_csv(src, dst, wide, root=root, batch_rows=a.batch_rows)
+            row["driver_s"] = round(time.perf_counter() - t0, 3)
+            row["driver_images_per_s"] = round(n / row["driver_s"], 1)
+            pool = DecodePool(group=1)
+            t0 = time.perf_counter()
+            imgs = [DecodePool.get([f])[0][0] for f in pool.submit(paths)]
+            row["decode_pool_alone_s"] = round(time.perf_counter() - t0, 3)
+            row["decode_workers"] = pool.workers
+            pool.close()
+            step = 2 * a.batch_rows
+            wide.caption(imgs[:step])
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(0, n, step):
+                wide.caption(imgs[i:i + step])
+            row["gpu_alone_wide_s"] = round(time.perf_counter() - t0, 3)
+            m.invalidate_caches()
+            narrow = Captioner(m, tokenizer=IdTokenizer())
+            narrow.caption(imgs[:32])  # captures the 32-row graph
+            t0 = time.perf_counter()
+            for i in range(0, n, 32):
+                with_decode = [np.asarray(Image.open(q).convert("RGB")) for q in paths[i:i + 32]]
+                narrow.caption(with_decode)
+            row["narrow_inline_decode_s"] = round(time.perf_counter() - t0, 3)
+            row["narrow_images_per_s"] = round(n / row["narrow_inline_decode_s"], 1)
+            t0 = time.perf_counter()
+            for i in range(0, n, 32):
+                narrow.caption(imgs[i:i + 32])
+            row["gpu_alone_narrow_s"] = round(time.perf_counter() - t0, 3)
+            m.invalidate_caches()
+            res["csv"].append(row)
+            print(row, file=sys.stderr, flush=True)
+    _emit(res, a)
 
 
 PROCESSORS = dict(repetition_penalty=1.3, no_repeat_ngram_size=2, min_new_tokens=12, suppress_tokens=[100, 101, 103])
@@ -346,7 +456,15 @@ def main():
     ap.add_argument("--temperature", type=float, default=1.0)
     ap.add_argument("--num-return-sequences", type=int, default=1)
     ap.add_argument("--processors", action="store_true", help="time generate with the logits processors off and on")
+    ap.add_argument("--lm-head-wide", action="store_true", help="time the LM head alone, narrow at 32 rows and wide up to 256")
+    ap.add_argument("--csv", type=int, default=0, help="time mmfd.caption.process_csv on this many synthetic JPEGs")
+    ap.add_argument("--csv-side", type=int, default=400, help="--csv: side of the synthetic JPEGs")
+    ap.add_argument("--batch-rows", type=int, default=64, help="--csv: rows per batch of the driver")
     a = ap.parse_args()
+    if a.lm_head_wide:
+        return wide_head_main(a)
+    if a.csv:
+        return csv_main(a)
     if a.processors:
         a.reps = max(a.reps, 7)
         return processors_main(a)
@@ -378,8 +496,9 @@ def main():
             row["tokens"] = int(gen(px, True).shape[1]) - 1
             res["generate"].append(row)
             print(row, file=sys.stderr, flush=True)
-            res["lm_head"].append(dict(lm_head_rate(dt, B * nb), precision=prec))
-            print(res["lm_head"][-1], file=sys.stderr, flush=True)
+            if nb == 1 or B * nb <= 32:
+                res["lm_head"].append(dict(lm_head_rate(dt, B * nb), precision=prec))
+                print(res["lm_head"][-1], file=sys.stderr, flush=True)
             if nb > 1:
                 res["beam_step"].append(dict(beam_step_times(dt, B, nb), precision=prec))
                 print(res["beam_step"][-1], file=sys.stderr, flush=True)
