@@ -240,6 +240,19 @@ typedef struct mmfd_attn_args {
 
 int mmfd_attn_fwd(const mmfd_attn_args* args, mmfd_stream_t stream);
 int mmfd_attn_bwd(const mmfd_attn_args* args, mmfd_stream_t stream);
+/* The gradient of a per-batch rel_bias under attention dropout (DeBERTa's c2p + p2c bias when the model
+   trains with attention_probs_dropout_prob > 0; mmfd_attn_args.d_rel_bias covers dropout_p = 0 only):
+     ds_out[b][h][q][k] = P (dP - delta),   P = exp(scale q.k + key_bias + rel_bias - lse),
+     dP = M (dO V^T) / (1 - p),             M = the keep mask the forward drew (re-hashed from seed, salt)
+   fp32 [B][H][Lq][Lk], contiguous, 16-B aligned, written once. `args` are the arguments of the preceding
+   mmfd_attn_bwd call (made without d_rel_bias): q, k, v, dout, lse, key_bias, rel_bias (rel_bias_sb =
+   H*Lq*Lk, rel_bias_mod = 0), scale, dropout_p, seed, salt as there, and delta holding what that call
+   left (rowsum(dO * O) = rowsum(P * dP) under dropout too). o, dq, dk, dv are not read or written;
+   drop_mask may be set and is not read (the mask is re-hashed: the same bits). Any Lq / Lk, D <= 64;
+   B*H <= 65535; ds_out must not alias rel_bias; no cosine attention. With dropout_p = 0 the result is
+   bit for bit the d_rel_bias of mmfd_attn_bwd. Masked key columns (key_bias) are exactly 0 in rows
+   that have a real key, and a row whose dO is 0 is 0. (Added within ABI 3: a symbol, no struct change.) */
+int mmfd_attn_bwd_ds(const mmfd_attn_args* args, float* ds_out, mmfd_stream_t stream);
 /* fp32 attention (the reference's SDPA / softmax(QK^T)V in fp32, layers.py:44-56 and the HF encoders'
    self-attention): mode 1 (default; env MMFD_FP32_ATTN=native, or MMFD_FP32_GEMM=native without it,
    selects 0 at load) runs every product on split bf16 operands (x = hi + mid + lo, six MFMA products

@@ -106,6 +106,26 @@ class CachedWeights:
         return r
 
 
+class StepSeeded:
+    """Mixin for the encoders that train with dropout (BertModel, DebertaV2Model): the device-resident
+    dropout seed. manual_seed(seed) sets it; every training forward takes a snapshot for its
+    forward/backward pair and advances it by a kernel (_fork_seed), so a captured step draws new masks
+    at every replay."""
+    _seed = None
+    _seed_value = 0
+
+    def manual_seed(self, seed):
+        self._seed_value = int(seed)
+        if self._seed is not None:
+            self._seed.set(self._seed_value)
+        return self
+
+    def _fork_seed(self, dev):
+        if self._seed is None or self._seed.t.device != dev:
+            self._seed = K.Seed(self._seed_value, device=dev)
+        return self._seed.fork()
+
+
 ATTN_DROP_MASK = os.environ.get("MMFD_ATTN_DROP_MASK") == "1"
 
 

@@ -183,6 +183,14 @@ Kern fwd_v2_kern(const AttnP& p) {
   return KERN_TD(attn_fwd_v2_kernel, HPB, false, 0);
 }
 
+// the dS kernel: the dropout-free instantiation keeps the name it has had in the plan export
+// (attn_bwd_ds_kernel<T,D>), the dropout one prints its flag (attn_bwd_ds_kernel<T,D,1>)
+template <typename T, int D, bool DROP>
+Kern ds_kern() {
+  if constexpr (DROP) return KERN_TD(attn_bwd_ds_kernel, true);
+  else return Kern{(const void*)&attn_bwd_ds_kernel<T, D, false>, "attn_bwd_ds_kernel", sizeof(T) == 2, KERN_REST(D)};
+}
+
 template <typename T, int D, bool REL, int MODE>
 void add_bwd_v2(Plan& pl, AttnP& p, const char* what) {
   constexpr int NTH = V2T<T>::DKDV_THREADS;
@@ -251,7 +259,61 @@ void plan_kernels(Plan& pl, AttnP& p, const mmfd_attn_args& a, bool bwd) {
            dim3((unsigned)std::min<int64_t>((words + 255) / 256, 8192)), 256, 0, 0, "attn_fwd dm_fill");
   }
   if (bwd && a.d_rel_bias)  // after the kernels above: it reads the delta they wrote
-    pl.add(KERN_TD(attn_bwd_ds_kernel), qblocks, 256, stream_kv_lds<T, D>(), 0, "attn_bwd d_rel_bias");
+    pl.add(ds_kern<T, D, false>(), qblocks, 256, stream_kv_lds<T, D>(), 0, "attn_bwd d_rel_bias");
+}
+
+// ---------------------------------------------------------------------------------------------
+// mmfd_attn_bwd_ds: dS alone, with or without dropout, after an mmfd_attn_bwd of the same arguments
+// ---------------------------------------------------------------------------------------------
+// Checks as for d_rel_bias (fill) without what the kernel does not touch (o, dq, dk, dv); the AttnP
+// fields attn_bwd_ds_kernel reads, the rest zero.
+int make_ds_plan(const mmfd_attn_args* a, const float* ds_out, AttnP& p, Plan& pl) {
+  MMFD_CHECK_STRUCT(a, mmfd_attn_args, "mmfd_attn_bwd_ds");
+  pl.n = 0;
+  pl.split3 = false;
+  pl.family = STREAM;
+  MMFD_CHECK_ARG(a->dtype == MMFD_F32 || a->dtype == MMFD_BF16, "attn_bwd_ds: bad dtype");
+  MMFD_CHECK_ARG(a->D > 0 && a->D <= 64, "attn_bwd_ds: head_dim %lld unsupported (<= 64)", (long long)a->D);
+  MMFD_CHECK_ARG(a->B >= 0 && a->H > 0 && a->Lq >= 0 && a->Lk > 0, "attn_bwd_ds: bad shape");
+  MMFD_CHECK_ARG(a->q && a->k && a->v && a->dout && a->lse && a->delta && ds_out, "attn_bwd_ds: null pointer");
+  const int epc = a->dtype == MMFD_BF16 ? 8 : 4;
+  MMFD_CHECK_ARG(a->D % epc == 0, "attn_bwd_ds: head_dim*element_size must be a multiple of 16 bytes");
+  auto al = [&](const void* ptr, int64_t sb, int64_t st) {
+    return ((uintptr_t)ptr & 15) == 0 && sb % epc == 0 && st % epc == 0;
+  };
+  MMFD_CHECK_ARG(al(a->q, a->q_sb, a->q_st) && al(a->k, a->k_sb, a->k_st) && al(a->v, a->v_sb, a->v_st) &&
+                     al(a->dout, a->do_sb, a->do_st),
+                 "attn_bwd_ds: q/k/v/dout must be 16-B aligned with strides multiple of 16 B");
+  MMFD_CHECK_ARG(a->rel_bias && a->rel_bias_sb == a->H * a->Lq * a->Lk && a->rel_bias_mod == 0,
+                 "attn_bwd_ds: needs a per-batch rel_bias [B][H][Lq][Lk] (rel_bias_sb = H*Lq*Lk, rel_bias_mod = 0)");
+  MMFD_CHECK_ARG(a->dropout_p <= 0.f || a->seed, "attn_bwd_ds: dropout needs seed");
+  MMFD_CHECK_ARG(a->dropout_p < 1.f, "attn_bwd_ds: dropout p must be < 1");
+  MMFD_CHECK_ARG(ds_out != a->rel_bias, "attn_bwd_ds: the output must not alias rel_bias");
+  MMFD_CHECK_ARG(((uintptr_t)ds_out & 15) == 0, "attn_bwd_ds: the output must be 16-B aligned");
+  MMFD_CHECK_ARG(a->B * a->H <= 65535, "attn_bwd_ds: needs B*H <= 65535");
+  MMFD_CHECK_ARG(a->cos_logit_scale == nullptr, "attn_bwd_ds: cosine attention is inference-only");
+  MMFD_CHECK_ARG(!a->drop_mask || ((uintptr_t)a->drop_mask & 3) == 0, "attn_bwd_ds: drop_mask must be 4-B aligned");
+  p = AttnP{};
+  p.B = a->B; p.H = a->H; p.Lq = a->Lq; p.Lk = a->Lk; p.scale = a->scale; p.D = (int)a->D;
+  p.q = a->q; p.q_sb = a->q_sb; p.q_st = a->q_st;
+  p.k = a->k; p.k_sb = a->k_sb; p.k_st = a->k_st;
+  p.v = a->v; p.v_sb = a->v_sb; p.v_st = a->v_st;
+  p.dout = a->dout; p.do_sb = a->do_sb; p.do_st = a->do_st;
+  p.lse = a->lse; p.delta = a->delta; p.key_bias = a->key_bias;
+  p.rel_bias = a->rel_bias; p.rb_sb = a->rel_bias_sb;
+  p.p = a->dropout_p > 0.f ? a->dropout_p : 0.f; p.thr16 = mmfd_drop_threshold16(p.p); p.kp = (a->Lk + 1) / 2;
+  p.keep_scale = 1.0f / (1.0f - p.p); p.seed = a->seed; p.salt = a->salt;
+  p.idx32 = (uint64_t)a->B * (uint64_t)a->H * (uint64_t)a->Lq * (uint64_t)a->Lk <= (1ull << 32);
+  p.dmw = (int)((a->Lk + 31) / 32);  // (drop_mask is not read: the kernel re-hashes the same bits)
+  if (p.B == 0 || p.Lq == 0) return 0;
+  const dim3 qblocks((unsigned)((p.Lq + 63) / 64), (unsigned)(p.B * p.H));
+  const bool bf = a->dtype == MMFD_BF16, drop = p.p > 0.f, wide = a->D > 32;
+  const char* what = "attn_bwd_ds";
+#define DS_ADD(T, D) pl.add(drop ? ds_kern<T, D, true>() : ds_kern<T, D, false>(), qblocks, 256, stream_kv_lds<T, D>(), 0, what)
+  if (bf) { if (wide) DS_ADD(bf16, 64); else DS_ADD(bf16, 32); }
+  else { if (wide) DS_ADD(float, 64); else DS_ADD(float, 32); }
+#undef DS_ADD
+  return 0;
 }
 
 // check the arguments, fill AttnP (with the host-set flags that steer the kernels: pl / pl_only, vst,
@@ -297,8 +359,7 @@ int make_plan(const mmfd_attn_args* a, bool bwd, AttnP& p, Plan& pl) {
   return 0;
 }
 
-int run_plan(const Plan& pl, const AttnP& p, const mmfd_attn_args& a, bool bwd, mmfd_stream_t stream) {
-  float* ds = (float*)a.d_rel_bias;
+int run_plan(const Plan& pl, const AttnP& p, const mmfd_attn_args& a, bool bwd, mmfd_stream_t stream, float* ds) {
   void* args[] = {(void*)&p, (void*)&ds};  // every kernel takes the AttnP; attn_bwd_ds_kernel its output too
   for (int i = 0; i < pl.n; ++i) {
     const Step& st = pl.step[i];
@@ -318,13 +379,19 @@ int attn_call(const mmfd_attn_args* a, bool bwd, mmfd_stream_t stream) {
   AttnP p;
   Plan pl;
   int rc = make_plan(a, bwd, p, pl);
-  return rc ? rc : run_plan(pl, p, *a, bwd, stream);
+  return rc ? rc : run_plan(pl, p, *a, bwd, stream, (float*)a->d_rel_bias);
 }
 
 }  // namespace
 
 extern "C" int mmfd_attn_fwd(const mmfd_attn_args* a, mmfd_stream_t stream) { return attn_call(a, false, stream); }
 extern "C" int mmfd_attn_bwd(const mmfd_attn_args* a, mmfd_stream_t stream) { return attn_call(a, true, stream); }
+extern "C" int mmfd_attn_bwd_ds(const mmfd_attn_args* a, float* ds_out, mmfd_stream_t stream) {
+  AttnP p;
+  Plan pl;
+  int rc = make_ds_plan(a, ds_out, p, pl);
+  return rc ? rc : run_plan(pl, p, *a, true, stream, ds_out);
+}
 
 // The plan of a call as text, without launching anything or touching HIP (not part of
 // include/mmfd.h; the pointers in `a` are never dereferenced). One line "family=<name>", then one
@@ -332,12 +399,13 @@ extern "C" int mmfd_attn_bwd(const mmfd_attn_args* a, mmfd_stream_t stream) { re
 // dynamic LDS bytes and the names of the host-set AttnP flags that are on (pl, pl_only, vst, dm,
 // dm_lds, idx32; pl_stride with pl); "mmfd_split3 rows= W=" when the split follows.
 // An empty call writes an empty string. Returns the argument checks' code.
+// bwd = 2: the plan of mmfd_attn_bwd_ds for these arguments, with a->d_rel_bias standing for ds_out.
 extern "C" int mmfd_debug_attn_plan(const mmfd_attn_args* a, int bwd, char* buf, int64_t bytes) {
   MMFD_CHECK_ARG(buf && bytes > 0, "mmfd_debug_attn_plan: no buffer");
   AttnP p;
   Plan pl;
   buf[0] = 0;
-  int rc = make_plan(a, bwd != 0, p, pl);
+  int rc = bwd == 2 ? make_ds_plan(a, a ? a->d_rel_bias : nullptr, p, pl) : make_plan(a, bwd != 0, p, pl);
   if (rc || pl.n == 0) return rc;
   int64_t at = 0;
   auto put = [&](const char* fmt, auto... v) {

@@ -356,9 +356,15 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(AttnP p) {
 // attn_bwd_dq_kernel: S^T = K Q^T and dP^T = V dO^T on MFMAs put the query on the lane, so lse and
 // delta are lane-local, and a lane holds 4 consecutive keys of its query:
 //   dS[q][k] = P (dP - delta),  P = exp(scale q.k + key_bias[k] + rel_bias[q][k] - lse[q])
-// (no `scale`: the bias enters S unscaled; no dropout: mmfd_attn_bwd refuses the combination).
-// It runs after the dQ / dK/dV kernels of the same call and reads the delta they left; those
-// kernels are untouched. Stores are 16-B vector stores when Lk % 4 == 0, else 4-B ones.
+// (no `scale`: the bias enters S unscaled). It runs after the dQ / dK/dV kernels of the same call
+// (mmfd_attn_bwd's d_rel_bias, DROP = false: that entry refuses dropout) or of the preceding call
+// (mmfd_attn_bwd_ds, either instantiation) and reads the delta they left; those kernels are
+// untouched. Stores are 16-B vector stores when Lk % 4 == 0, else 4-B ones.
+//
+// DROP: dP = M (dO V^T) / (1 - p) with the keep mask M the forward drew — delta = rowsum(dO * O) =
+// rowsum(P * dP) holds under dropout as well, so dS = P (dP - delta) stands. The lane's 4 consecutive
+// keys start at a multiple of 4: two key pairs, two hashes (pair_keep). A template argument, not a
+// run-time flag: the dropout-free instantiation carries no hash code (see the x6 forward).
 //
 // Masked keys come out exactly 0: key_bias of a masked key is -FLT_MAX (mmfd_mask_to_bias), which
 // absorbs the finite rest of the score, while lse of a row with at least one real key is finite, so
@@ -369,7 +375,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(AttnP p) {
 // zeroes dO of those rows first, mmfd_attn_fill_masked_rows_bwd, which makes their dS 0 as well.)
 constexpr float DS_EXP_MIN = -104.f;
 
-template <typename T, int D>
+template <typename T, int D, bool DROP>
 __global__ void __launch_bounds__(256) attn_bwd_ds_kernel(AttnP p, float* __restrict__ ds_out) {
   using C = AT<T, D>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -394,6 +400,8 @@ __global__ void __launch_bounds__(256) attn_bwd_ds_kernel(AttnP p, float* __rest
   const float* relrow = p.rel_bias + rowoff;
   float* dsrow = ds_out + rowoff;
   const bool vec4 = (p.Lk & 3) == 0;  // rows then start 16-B aligned (base alignment checked by the host)
+  uint32_t hkey = 0u;
+  if constexpr (DROP) hkey = mmfd_hash_key(*p.seed, p.salt);
 
   for (int64_t k0 = 0; k0 < p.Lk; k0 += 64) {
     __syncthreads();
@@ -411,6 +419,11 @@ __global__ void __launch_bounds__(256) attn_bwd_ds_kernel(AttnP p, float* __rest
       const int64_t key0 = k0 + ks * 16 + 4 * g;
       if (!qok || key0 >= p.Lk) continue;
       float ds[4];
+      float z[4] = {1.f, 1.f, 1.f, 1.f};
+      if constexpr (DROP) {  // keys key0, key0 + 1 | key0 + 2, key0 + 3 (a pair past Lk is hashed and not used)
+        const int64_t row = bh * p.Lq + myq;
+        keep4_pairs(attn_hash64(hkey, p, row, key0), attn_hash64(hkey, p, row, key0 + 2), p, z);
+      }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int64_t key = key0 + r;
@@ -420,7 +433,8 @@ __global__ void __launch_bounds__(256) attn_bwd_ds_kernel(AttnP p, float* __rest
           if (p.key_bias) sc += p.key_bias[b * p.Lk + key];
           const float x = sc - lse;
           const float pr = x < DS_EXP_MIN ? 0.f : __expf(x);
-          ds[r] = pr * (dp[r] - dlt);
+          if constexpr (DROP) ds[r] = pr * (dp[r] * z[r] - dlt);
+          else ds[r] = pr * (dp[r] - dlt);
         }
       }
       if (vec4) {

@@ -27,8 +27,27 @@ like encoders._BertFn) whose backward is `deberta_backward`: the post-LN layer b
 through the disentangled bias the attention backward's dS (mmfd_attn_args.d_rel_bias), its scatter
 back to dc2p / dp2c (mmfd_deberta_rel_bias_bwd), four per-head GEMMs into dQ, dK and the position
 projections' gradients, and the padded-row fix-up's adjoint (mmfd_attn_fill_masked_rows_bwd). Each
-layer keeps its [B, H, L, L] fp32 bias for the backward (DESIGN f1). Dropout is not implemented on
-this path (HF's default is 0.1): the config's dropout probabilities must be 0 when training.
+layer keeps its [B, H, L, L] fp32 bias for the backward (DESIGN f1).
+
+Dropout (training mode of a trainable model, p = hidden_dropout_prob = attention_probs_dropout_prob > 0;
+mmfd's config defaults are 0 / 0, HF's 0.1 / 0.1) sits at HF's five sites, drawn from the counter hash
+all mmfd kernels share (site names "deberta.emb", "deberta.L<i>.pos | .attn | .attn_out | .ffn_out"; a
+hidden site's mask index is the flat index of its contiguous tensor):
+  embeddings    dropout(LayerNorm(word[id])) in the embedding kernel, then the mask (HF masks first;
+                the two commute)
+  positions     the layer's position projection reads dropout(LayerNorm(rel_embeddings)), one mask per
+                layer (HF's pos_dropout inside every DisentangledSelfAttention)
+  attention     dropout(P) inside the attention kernels; the backward takes dq / dk / dv from
+                mmfd_attn_bwd and the bias gradient dS = P (M dP / (1 - p) - delta) from mmfd_attn_bwd_ds
+  hidden        after the attention-output and the FFN-output projections (GEMM epilogues)
+One probability serves all five, as in BertModel: a training forward with two different values raises.
+The seed is device-resident (manual_seed; blocks.StepSeeded) and advances once per training forward.
+Fully padded query rows keep the inference rule under dropout: their attention output is the mean of V
+(mmfd_attn_fill_masked_rows) with NO attention dropout, their dO is zeroed before the attention backward
+so their dS is 0, and hidden dropout applies to them like to any row. (HF drops their uniform
+probabilities too; either way these rows are padding whose values no caller reads.)
+With p = 0, in eval mode or under no_grad the model launches exactly the kernels it launched before
+dropout existed; the p = 0 backward still takes dS from mmfd_attn_bwd's d_rel_bias.
 """
 from __future__ import annotations
 
@@ -61,7 +80,7 @@ class DebertaV2Config:
     pad_token_id: int = 0
     # fine-tuning (opt-in): with trainable=False the model is inference-only exactly as before
     trainable: bool = False
-    hidden_dropout_prob: float = 0.0            # (HF default 0.1; only 0 is implemented for training)
+    hidden_dropout_prob: float = 0.0            # (HF default 0.1; training takes one value for both)
     attention_probs_dropout_prob: float = 0.0
 
 
@@ -97,7 +116,7 @@ def _bias_indices(L, S, max_position, device):
     return t
 
 
-class DebertaV2Model(Bk.CachedWeights, nn.Module):
+class DebertaV2Model(Bk.CachedWeights, Bk.StepSeeded, nn.Module):
     def __init__(self, config: DebertaV2Config | None = None, **kw):
         super().__init__()
         c = config or DebertaV2Config(**kw)
@@ -168,9 +187,9 @@ class DebertaV2Model(Bk.CachedWeights, nn.Module):
             raise NotImplementedError("mmfd DebertaV2Model is inference-only (frozen encoder, train.py:335-340): "
                                       "call it under torch.no_grad() or freeze its parameters, or build it with "
                                       "DebertaV2Config(trainable=True)")
-        if c.trainable and self.training and (c.hidden_dropout_prob > 0 or c.attention_probs_dropout_prob > 0):
-            raise NotImplementedError("mmfd DebertaV2Model trains without dropout only: set hidden_dropout_prob and "
-                                      "attention_probs_dropout_prob to 0 (HF's default is 0.1)")
+        if c.trainable and self.training and c.hidden_dropout_prob != c.attention_probs_dropout_prob:
+            raise NotImplementedError("mmfd DebertaV2Model uses one dropout probability for hidden and attention "
+                                      "dropout: set hidden_dropout_prob = attention_probs_dropout_prob")
         if keep:
             out = _DebertaFn.apply(self, list(params.keys()), input_ids, attention_mask, *params.values())
             return EncoderOutput(last_hidden_state=out)
@@ -186,13 +205,16 @@ class DebertaV2Model(Bk.CachedWeights, nn.Module):
 DEBERTA_QKV = (".attention.self.query_proj", ".attention.self.key_proj", ".attention.self.value_proj")
 
 
-# x: layer input; qkv [B, L, 3D]; pos [2S, 3D]: position projections; rb [B, H, L, L] fp32: disentangled bias
-DebertaLayerState = namedtuple("DebertaLayerState", "x qkv pos rb lse post")
+# x: layer input; qkv [B, L, 3D]; pos [2S, 3D]: position projections; rb [B, H, L, L] fp32: disentangled bias;
+# relE [2S, D]: what the position projection read (the layer's dropped copy under dropout); akw: attn_fwd's
+# dropout keywords
+DebertaLayerState = namedtuple("DebertaLayerState", "x qkv pos rb lse post relE akw")
 
 
-def deberta_forward(model: DebertaV2Model, ctx: Bk.StepCtx, input_ids, attention_mask, st=None):
+def deberta_forward(model: DebertaV2Model, ctx: Bk.StepCtx, input_ids, attention_mask, st=None, site="deberta"):
     """`st` (a dict, training): filled with what deberta_backward reads; the kernels and their order
-    are the same either way, so the outputs are too"""
+    are the same either way, so the outputs are too. With ctx.p > 0 (a training-mode forward of a
+    trainable model) the five dropout sites of the module docstring are on."""
     cfg = model.config
     keep = st is not None
     dev = ctx.P["embeddings.word_embeddings.weight"].device
@@ -208,10 +230,11 @@ def deberta_forward(model: DebertaV2Model, ctx: Bk.StepCtx, input_ids, attention
     zp = model._zero_pos.get((L, str(dev)))
     if zp is None:
         zp = model._zero_pos[(L, str(dev))] = torch.zeros(L, D, device=dev, dtype=torch.float32)
+    emb_drop = ctx.drop(site + ".emb")
     if keep:
         s0, x, m0, r0 = K.embed_ln_train(ids, None, ctx.P["embeddings.word_embeddings.weight"], zp,
                                          ctx.P["embeddings.LayerNorm.weight"], ctx.P["embeddings.LayerNorm.bias"],
-                                         eps, dt)
+                                         eps, dt, **emb_drop)
     else:
         x = K.embed_ln_infer(ids, None, ctx.P["embeddings.word_embeddings.weight"], zp,
                              ctx.P["embeddings.LayerNorm.weight"], ctx.P["embeddings.LayerNorm.bias"], eps, dt)
@@ -226,9 +249,12 @@ def deberta_forward(model: DebertaV2Model, ctx: Bk.StepCtx, input_ids, attention
     p2c = torch.empty((H, B * L, 2 * S), device=dev, dtype=dt)
     for i in range(cfg.num_hidden_layers):
         p = f"encoder.layer.{i}"
+        s = f"{site}.L{i}"
         names = [p + n for n in DEBERTA_QKV]
         qkv = Bk.linear_packed(ctx, x, names)                # [B*L, 3D]
-        pos = Bk.linear_packed(ctx, relE, names)             # [2S, 3D]: posQ | posK | (unused V)
+        pdrop = ctx.drop(s + ".pos")                         # HF pos_dropout: a mask per layer on the one table
+        relE_i = K.dropout(relE, pdrop["dropout_p"], pdrop["seed"], pdrop["salt"]) if pdrop else relE
+        pos = Bk.linear_packed(ctx, relE_i, names)           # [2S, 3D]: posQ | posK | (unused V)
         for h in range(H):
             qh, kh = qkv[:, h * d:(h + 1) * d], qkv[:, D + h * d:D + (h + 1) * d]
             pqh, pkh = pos[:, h * d:(h + 1) * d], pos[:, D + h * d:D + (h + 1) * d]
@@ -236,16 +262,18 @@ def deberta_forward(model: DebertaV2Model, ctx: Bk.StepCtx, input_ids, attention
             K.gemm(kh, pqh, out=p2c[h])                      # p2c = K_h posQ_h^T
         rb = K.deberta_rel_bias(c2p, p2c, c2p_idx, p2c_idx, B, L, scale)
         q3 = qkv.view(B, L, 3 * D)
+        akw = ctx.attn_drop(s + ".attn", q3[..., :D], q3[..., D:2 * D], H)
         o, lse = K.attn_fwd(q3[..., :D], q3[..., D:2 * D], q3[..., 2 * D:], H, scale=scale, key_bias=key_bias,
-                            rel_bias=rb)
-        K.attn_fill_masked_rows(q3[..., 2 * D:], o, H, mask)
-        x_out, _, post = Bk.post_ln_fwd(ctx, x, o, p, BERT_LAYER, eps, keep=keep, planes=False)
+                            rel_bias=rb, **akw)
+        K.attn_fill_masked_rows(q3[..., 2 * D:], o, H, mask)  # (padded query rows: mean of V, no dropout)
+        x_out, _, post = Bk.post_ln_fwd(ctx, x, o, p, BERT_LAYER, eps, keep=keep, planes=False,
+                                        sites=(s + ".attn_out", s + ".ffn_out") if ctx.p > 0 else (None, None))
         if keep:
-            st["layers"].append(DebertaLayerState(x, q3, pos, rb, lse, post))
+            st["layers"].append(DebertaLayerState(x, q3, pos, rb, lse, post, relE_i, akw))
         x = x_out
     if keep:
         st.update(ids=ids, mask=mask, key_bias=key_bias, idx=(c2p_idx, p2c_idx), s0=s0, m0=m0, r0=r0, rel_in=rel_in,
-                  relE=relE, mr=mr, rr=rr, scale=scale, bufs=(c2p, p2c))
+                  mr=mr, rr=rr, scale=scale, bufs=(c2p, p2c), emb_drop=emb_drop, site=site)
     return x.view(B, L, D)
 
 
@@ -253,11 +281,14 @@ def deberta_backward(model: DebertaV2Model, ctx: Bk.StepCtx, dout, st):
     """Gradients of every parameter into ctx.grads, layers in reverse. Per layer: blocks.post_ln_bwd
     (FFN, both LayerNorms, output projection), then through the attention
         S = scale Q K^T + key_bias + inv (c2p[i, c2p_idx[i, j]] + p2c[j, p2c_idx[j, i]])
-    with c2p = Q_h posK_h^T, p2c = K_h posQ_h^T: attn_bwd also emits dS (no dropout), its scatter
-    gives dc2p / dp2c, and per head dQ_h += dc2p_h posK_h, dK_h += dp2c_h posQ_h, dposK_h =
+    with c2p = Q_h posK_h^T, p2c = K_h posQ_h^T: attn_bwd also emits dS (without dropout; under dropout
+    attn_bwd keeps its delta and attn_bwd_ds follows with the forward's mask), its scatter gives
+    dc2p / dp2c, and per head dQ_h += dc2p_h posK_h, dK_h += dp2c_h posQ_h, dposK_h =
     dc2p_h^T Q_h, dposQ_h = dp2c_h^T K_h. The packed Q|K|V weights collect two gradients: the token
-    stream (dqkv, x) and the position stream (dpos = dposQ | dposK, LayerNorm(rel_embeddings)); the
-    relative embeddings collect dpos W over all layers (fp32 accumulator)."""
+    stream (dqkv, x) and the position stream (dpos = dposQ | dposK, the layer's — under dropout
+    dropped — LayerNorm(rel_embeddings)); the relative embeddings collect dpos W over all layers (fp32
+    accumulator; under dropout each layer's term passes its position mask in the GEMM epilogue:
+    drelE += M_i (dpos W) / (1 - p))."""
     cfg = model.config
     ids, mask = st["ids"], st["mask"]
     B, L = ids.shape
@@ -266,12 +297,12 @@ def deberta_backward(model: DebertaV2Model, ctx: Bk.StepCtx, dout, st):
     S2 = 2 * model.att_span
     dt, scale = ctx.dt, st["scale"]
     c2p_idx, p2c_idx = st["idx"]
-    relE = st["relE"]
     dev = dout.device
     dx = Bk.as2d(dout).contiguous()
     dsb = torch.empty((B, H, L, L), device=dev, dtype=torch.float32)  # dS of one layer at a time
     dc2p, dp2c = st["bufs"]                     # the forward's c2p / p2c buffers, free by now
     drelE = torch.empty((S2, D), device=dev, dtype=torch.float32)
+    delta = torch.empty((B, H, L), device=dev, dtype=torch.float32) if ctx.p > 0 else None  # attn_bwd -> attn_bwd_ds
     for i in reversed(range(cfg.num_hidden_layers)):
         ls = st["layers"][i]
         st["layers"][i] = None
@@ -279,8 +310,14 @@ def deberta_backward(model: DebertaV2Model, ctx: Bk.StepCtx, dout, st):
         do, ds1 = Bk.post_ln_bwd(ctx, dx, ls.post)
         # padded query rows: their dO goes to dV of every key (mean of V in the forward), not into the attention
         gsum = K.attn_fill_masked_rows_bwd(do, H, mask)
-        dqkv, _, _ = Bk.attn_bwd_packed(ctx, ls.qkv, ls.post.o, ls.lse, do, H, planes=False, scale=scale,
-                                        key_bias=st["key_bias"], rel_bias=ls.rb, d_rel_bias=dsb)
+        if ctx.p > 0:  # mmfd_attn_bwd refuses d_rel_bias with dropout: dS from its own entry, on the delta kept here
+            dqkv, _, _ = Bk.attn_bwd_packed(ctx, ls.qkv, ls.post.o, ls.lse, do, H, planes=False, scale=scale,
+                                            key_bias=st["key_bias"], rel_bias=ls.rb, delta=delta, **ls.akw)
+            K.attn_bwd_ds(ls.qkv[..., :D], ls.qkv[..., D:2 * D], ls.qkv[..., 2 * D:], ls.lse, do, H, delta,
+                          rel_bias=ls.rb, key_bias=st["key_bias"], scale=scale, out=dsb, **ls.akw)
+        else:
+            dqkv, _, _ = Bk.attn_bwd_packed(ctx, ls.qkv, ls.post.o, ls.lse, do, H, planes=False, scale=scale,
+                                            key_bias=st["key_bias"], rel_bias=ls.rb, d_rel_bias=dsb)
         K.attn_fill_masked_rows_bwd(do, H, mask, dv=dqkv.view(B, L, 3 * D)[..., 2 * D:], gsum=gsum)
         K.deberta_rel_bias_bwd(dsb, c2p_idx, p2c_idx, B, L, scale, S2, dt, dc2p=dc2p, dp2c=dp2c)
         dpos = torch.empty((S2, 2 * D), device=dev, dtype=dt)  # dposQ | dposK (the V third of pos is unused)
@@ -293,9 +330,10 @@ def deberta_backward(model: DebertaV2Model, ctx: Bk.StepCtx, dout, st):
         names = [f"encoder.layer.{i}" + n for n in DEBERTA_QKV]
         # (as blocks.self_attn_bwd, with the position stream's GEMMs between the weight and data gradients)
         ctx.lin_grads(names, dqkv, ls.x)                # token stream (one packed GEMM)
-        ctx.lin_grads(names[:2], dpos, relE)            # position stream: accumulates onto the Q and K blocks
+        ctx.lin_grads(names[:2], dpos, ls.relE)         # position stream: accumulates onto the Q and K blocks
         Wp, _ = ctx.w_packed(names)
-        K.gemm(dpos, Wp[:2 * D], trans_b=True, out=drelE, beta=0.0 if i == cfg.num_hidden_layers - 1 else 1.0)
+        K.gemm(dpos, Wp[:2 * D], trans_b=True, out=drelE, beta=0.0 if i == cfg.num_hidden_layers - 1 else 1.0,
+               **ctx.drop(f"{st['site']}.L{i}.pos"))
         dx = Bk.linear_dx(ctx, dqkv, Wp, residual=ds1)  # dx_in = ds1 + dQKV [Wq;Wk;Wv]
         ctx.flush_ready()
     # relative embeddings: LayerNorm backward of the summed position gradient
@@ -304,8 +342,10 @@ def deberta_backward(model: DebertaV2Model, ctx: Bk.StepCtx, dout, st):
     grel = K.zeros(ctx.P["encoder.rel_embeddings.weight"].shape, device=dev)  # rows past 2S (none by default): 0
     K.cast(drel, torch.float32, out=grel[:S2])
     ctx.grads["encoder.rel_embeddings.weight"] = grel
-    # embeddings: x = LayerNorm(word[id]) * mask
+    # embeddings: x = dropout(LayerNorm(word[id])) * mask
     K.mask_rows(dx, mask)
+    if st["emb_drop"]:
+        dx = K.dropout(dx, st["emb_drop"]["dropout_p"], st["emb_drop"]["seed"], st["emb_drop"]["salt"])
     dsum, _ = Bk.layernorm_bwd(ctx, dx, st["s0"], "embeddings.LayerNorm", st["m0"], st["r0"])
     dword = K.zeros(ctx.P["embeddings.word_embeddings.weight"].shape, device=dev)
     K.embed_bwd(ids, None, dsum, dword, None, None, padding_idx=cfg.pad_token_id)
@@ -316,7 +356,10 @@ def deberta_backward(model: DebertaV2Model, ctx: Bk.StepCtx, dout, st):
 class _DebertaFn(torch.autograd.Function):
     @staticmethod
     def forward(fctx, model, names, input_ids, attention_mask, *params):
-        sc = Bk.module_ctx(model, names, params)
+        cfg = model.config
+        p = cfg.hidden_dropout_prob if model.training else 0.0  # (== attention_probs_dropout_prob: forward() checked)
+        dev = params[0].device
+        sc = Bk.module_ctx(model, names, params, p, model._fork_seed(dev) if p > 0 else None)
         st = {"layers": []}
         out = deberta_forward(model, sc, input_ids, attention_mask, st=st)
         fctx.sc, fctx.st, fctx.model, fctx.names = sc, st, model, names

@@ -58,7 +58,7 @@ class EncoderOutput:
 # -------------------------------------------------------------------------------------------------
 # BERT
 # -------------------------------------------------------------------------------------------------
-class BertModel(Bk.CachedWeights, nn.Module):
+class BertModel(Bk.CachedWeights, Bk.StepSeeded, nn.Module):
     """HF BertModel (add_pooling_layer=False) parameter layout; forward returns .last_hidden_state."""
 
     def __init__(self, config: BertConfig | None = None, **kw):
@@ -89,8 +89,6 @@ class BertModel(Bk.CachedWeights, nn.Module):
             L.output.LayerNorm = nn.LayerNorm(D, eps=c.layer_norm_eps)
             self.encoder.layer.append(L)
         self.compute_dtype = torch.float32
-        self._seed = None
-        self._seed_value = 0
         self._init_weights()
 
     def _init_weights(self, std=0.02):
@@ -110,17 +108,6 @@ class BertModel(Bk.CachedWeights, nn.Module):
     def set_precision(self, precision):
         self.compute_dtype = {"fp32": torch.float32, "bf16": torch.bfloat16}[precision]
         return self
-
-    def manual_seed(self, seed):
-        self._seed_value = int(seed)
-        if self._seed is not None:
-            self._seed.set(self._seed_value)
-        return self
-
-    def _fork_seed(self, dev):
-        if self._seed is None or self._seed.t.device != dev:
-            self._seed = K.Seed(self._seed_value, device=dev)
-        return self._seed.fork()
 
     def forward(self, input_ids, attention_mask=None, token_type_ids=None, **unused):
         names = [n for n, _ in self.named_parameters()]

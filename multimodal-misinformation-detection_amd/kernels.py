@@ -154,6 +154,7 @@ SIGNATURES = {
     "mmfd_colsum": (_I, [_I, _I64, _I64, _VP, _I64, _VP, _F, _VP, _I64, _VP]),
     "mmfd_attn_fwd": (_I, [ctypes.POINTER(AttnArgs), _VP]),
     "mmfd_attn_bwd": (_I, [ctypes.POINTER(AttnArgs), _VP]),
+    "mmfd_attn_bwd_ds": (_I, [ctypes.POINTER(AttnArgs), _VP, _VP]),
     "mmfd_layernorm_fwd": (_I, [_I, _I64, _I64, _VP, _I64, _VP, _VP, _F, _VP, _I64, _VP, _VP, _VP]),
     "mmfd_layernorm_bwd": (_I, [_I, _I64, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP, _I64, _VP, _I64,
                                 _VP, _VP, _F, _VP, _F, _VP, _U64, _VP, _I64, _VP]),
@@ -856,6 +857,59 @@ def attn_bwd(q, k, v, o, lse, dout, H, *, dq=None, dk=None, dv=None, scale=None,
     return dq, dk, dv
 
 
+def attn_bwd_ds(q, k, v, lse, dout, H, delta, *, rel_bias, key_bias=None, scale=None, dropout_p=0.0, seed=None, salt=0,
+                drop_mask=None, out=None):
+    """The gradient of a per-batch `rel_bias` [B, H, Lq, Lk] with or without attention dropout: fp32
+    [B, H, Lq, Lk] = P (M (dO V^T) / (1 - p) - delta) with the forward's keep mask M (include/mmfd.h
+    mmfd_attn_bwd_ds). The arguments are those of the preceding attn_bwd call — made without d_rel_bias,
+    which refuses dropout — and `delta` the tensor that call was given. Nothing but `out` is written.
+    `drop_mask` (the forward's keep-bitmask) is accepted and not read: the kernel re-hashes the same bits.
+    With dropout_p = 0 the result is bit for bit attn_bwd's d_rel_bias."""
+    _require_cuda(q, k, v, lse, dout, delta, rel_bias, key_bias, out)
+    B, Lq, HD = q.shape
+    Lk = k.shape[1]
+    D = HD // H
+    rb, rb_sb, rb_mod = _rel_bias_args(rel_bias, B, H, Lq, Lk)  # (a shared or modulo bias: the library refuses it)
+    if rb is None:
+        raise ValueError("attn_bwd_ds: no rel_bias")
+    if delta.dtype != torch.float32 or not delta.is_contiguous() or delta.numel() != B * H * Lq:
+        raise ValueError("attn_bwd_ds: delta must be the contiguous fp32 [B, H, Lq] tensor attn_bwd filled")
+    if lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() != B * H * Lq:
+        raise ValueError("attn_bwd_ds: lse must be contiguous fp32 [B, H, Lq]")
+    if key_bias is not None and (key_bias.dtype != torch.float32 or not key_bias.is_contiguous()
+                                 or key_bias.numel() != B * Lk):
+        raise ValueError("attn_bwd_ds: key_bias must be contiguous fp32 [B, Lk]")
+    if tuple(k.shape) != (B, Lk, HD) or tuple(v.shape) != (B, Lk, HD) or tuple(dout.shape) != (B, Lq, HD):
+        raise ValueError("attn_bwd_ds: k, v must be [B, Lk, H*D] and dout [B, Lq, H*D]")
+    for t in (k, v, dout):
+        if t.dtype != q.dtype:
+            raise TypeError("attn_bwd_ds: q, k, v, dout must share a dtype")
+    if drop_mask is not None and (drop_mask.dtype != torch.int32 or not drop_mask.is_contiguous()
+                                  or drop_mask.numel() != B * H * Lq * ((Lk + 31) // 32)):
+        raise ValueError("attn_bwd_ds: drop_mask must be the drop_mask_buffer of the forward call")
+    if out is None:
+        out = torch.empty((B, H, Lq, Lk), device=q.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (B, H, Lq, Lk):
+        raise ValueError(f"attn_bwd_ds: out must be contiguous fp32 {(B, H, Lq, Lk)}")
+    a = AttnArgs()
+    a.dtype = dtype_code(q.dtype)
+    a.B, a.H, a.Lq, a.Lk, a.D = B, H, Lq, Lk, D
+    a.scale = float(scale if scale is not None else D ** -0.5)
+    a.q, a.q_sb, a.q_st = _head_view(q, H, D)
+    a.k, a.k_sb, a.k_st = _head_view(k, H, D)
+    a.v, a.v_sb, a.v_st = _head_view(v, H, D)
+    a.dout, a.do_sb, a.do_st = _head_view(dout, H, D)
+    a.lse, a.delta = lse.data_ptr(), delta.data_ptr()
+    a.key_bias = key_bias.data_ptr() if key_bias is not None else None
+    a.rel_bias, a.rel_bias_sb, a.rel_bias_mod = rb, rb_sb, rb_mod
+    a.dropout_p = float(dropout_p)
+    a.seed = seed.t.data_ptr() if seed is not None else None
+    a.salt = int(salt) & 0xFFFFFFFFFFFFFFFF
+    a.drop_mask = drop_mask.data_ptr() if drop_mask is not None and dropout_p > 0 else None
+    _check(lib().mmfd_attn_bwd_ds(ctypes.byref(a), _ptr(out), _stream()), "mmfd_attn_bwd_ds")
+    return out
+
+
 def attn_bwd_bias_sum(q, k, v, o, lse, dout, H, delta, *, rel_bias, rel_bias_mod=None, scale=None, key_bias=None,
                       dropout_p=0.0, cos_logit_scale=None, out=None):
     """The gradient of a `rel_bias` shared by the batch ([H, Lq, Lk]) or read with a batch modulus
@@ -1094,9 +1148,10 @@ def embed_ln_infer(ids, pos_ids, word, pos, gamma, beta, eps, dtype, tts=None, t
     return y
 
 
-def embed_ln_train(ids, pos_ids, word, pos, gamma, beta, eps, dtype):
+def embed_ln_train(ids, pos_ids, word, pos, gamma, beta, eps, dtype, dropout_p=0.0, seed=None, salt=0):
     """embed_ln_infer that keeps what the LayerNorm backward reads: (sum, y, mean, rstd) with
-    sum = word[id] + pos[pos_id] before the LayerNorm (no type table, no dropout)"""
+    sum = word[id] + pos[pos_id] before the LayerNorm (no type table); with dropout_p > 0
+    y = dropout(LayerNorm(sum)), element index = the flat index of y (as embed_ln_fwd)"""
     B, L = ids.shape
     D = word.shape[1]
     dev = ids.device
@@ -1107,7 +1162,8 @@ def embed_ln_train(ids, pos_ids, word, pos, gamma, beta, eps, dtype):
     _check(lib().mmfd_embed_ln_fwd_ex(dtype_code(dtype), B, L, D, _ptr(ids.contiguous()),
                                       _ptr(pos_ids.contiguous()) if pos_ids is not None else None, None, _ptr(word),
                                       _ptr(pos), None, _ptr(gamma), _ptr(beta), float(eps), _ptr(s), _ptr(y),
-                                      _ptr(mean), _ptr(rstd), 0.0, None, 0, _stream()), "mmfd_embed_ln_fwd_ex")
+                                      _ptr(mean), _ptr(rstd), float(dropout_p), seed.ptr() if seed is not None else None,
+                                      int(salt) & 0xFFFFFFFFFFFFFFFF, _stream()), "mmfd_embed_ln_fwd_ex")
     return s, y, mean, rstd
 
 

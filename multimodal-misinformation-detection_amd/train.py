@@ -14,6 +14,7 @@ from __future__ import annotations
 import argparse
 import logging
 import os
+import warnings
 
 import numpy as np
 import torch
@@ -436,8 +437,13 @@ def parse_args(argv=None):
                     help="microsoft/swinv2-base-patch4-window8-256 (frozen unless --train_image_encoder) or "
                          "google/vit-base-patch16-224")
     ap.add_argument("--train_text_encoder", action="store_true",
-                    help="fine-tune microsoft/deberta-v3-xsmall (no dropout) instead of freezing it; --freeze_text "
-                         "wins; no effect on bert-base-uncased, which trains unless --freeze_text")
+                    help="fine-tune microsoft/deberta-v3-xsmall instead of freezing it (dropout: --text_dropout, "
+                         "default 0); --freeze_text wins; no effect on bert-base-uncased, which trains unless "
+                         "--freeze_text")
+    ap.add_argument("--text_dropout", type=float, default=0.0,
+                    help="hidden and attention dropout probability of a trainable microsoft/deberta-v3-xsmall "
+                         "(transformers' default is 0.1); ignored with a warning when the text encoder is frozen or "
+                         "is bert-base-uncased, which keeps its own configuration's 0.1")
     ap.add_argument("--train_image_encoder", action="store_true",
                     help="fine-tune microsoft/swinv2-base-patch4-window8-256 (no stochastic depth) instead of freezing "
                          "it; --freeze_image wins; no effect on google/vit-base-patch16-224, which trains unless "
@@ -458,15 +464,25 @@ IMAGE_ENCODERS = ("microsoft/swinv2-base-patch4-window8-256", "google/vit-base-p
 def build_encoders(args, device):
     """the encoders of train.py:329-340 (random init: no hub download here). DeBERTa-v3 and Swinv2
     are inference encoders by default and then frozen; with --train_text_encoder (and no
-    --freeze_text) DeBERTa-v3 is built trainable (DebertaV2Config(trainable=True), dropout 0) and
-    fine-tuned, with --train_image_encoder (and no --freeze_image) Swinv2 is
-    (Swinv2Config(trainable=True), no stochastic depth); bert-base / ViT-B/16 train unless
-    --freeze_text / --freeze_image."""
+    --freeze_text) DeBERTa-v3 is built trainable (DebertaV2Config(trainable=True), hidden and
+    attention dropout --text_dropout, default 0) and fine-tuned, with --train_image_encoder (and no
+    --freeze_image) Swinv2 is (Swinv2Config(trainable=True), no stochastic depth); bert-base /
+    ViT-B/16 train unless --freeze_text / --freeze_image. --text_dropout reaches only a trainable
+    DeBERTa-v3: elsewhere it is ignored with a warning."""
+    text_dropout = float(getattr(args, "text_dropout", 0.0) or 0.0)
+    if not 0.0 <= text_dropout < 1.0:
+        raise ValueError(f"--text_dropout must be in [0, 1), got {text_dropout}")
     if args.text_encoder == "microsoft/deberta-v3-xsmall":
         from .deberta import DebertaV2Config, DebertaV2Model
         trainable = bool(getattr(args, "train_text_encoder", False)) and not args.freeze_text
-        text, text_frozen = DebertaV2Model(DebertaV2Config(trainable=trainable)), not trainable
+        if text_dropout > 0 and not trainable:
+            warnings.warn("--text_dropout is ignored: the text encoder is frozen (see --train_text_encoder)")
+        p = text_dropout if trainable else 0.0
+        text = DebertaV2Model(DebertaV2Config(trainable=trainable, hidden_dropout_prob=p, attention_probs_dropout_prob=p))
+        text_frozen = not trainable
     elif args.text_encoder == "bert-base-uncased":
+        if text_dropout > 0:
+            warnings.warn("--text_dropout is ignored: bert-base-uncased keeps its configuration's dropout")
         text, text_frozen = BertModel(BertConfig()), args.freeze_text
     else:
         raise ValueError(f"--text_encoder must be one of {TEXT_ENCODERS}")
