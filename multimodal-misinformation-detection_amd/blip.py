@@ -6,7 +6,7 @@ large").generate(**inputs)` over every claim and evidence image), and the captio
 
 `BlipForConditionalGeneration` keeps transformers' parameter names, so its `state_dict` loads with
 `strict=True`; `generate` follows transformers' greedy default (20 new tokens, decoding from [bos], stop
-at sep_token_id, pad afterwards) or, with num_beams > 1, its beam search (csrc/beam.hip; the last item below).
+at sep_token_id, pad afterwards) or, with num_beams > 1, its beam search (csrc/beam.hip).
 
 What runs where:
   * vision tower (pre-LN ViT, packed qkv): patchify + GEMM, class token + positions, then per layer
@@ -14,19 +14,17 @@ What runs where:
     (+ residual), and post_layernorm: the encoders' kernels (mmfd.blocks);
   * once per image and decoder layer the cross-attention K|V of the image tokens, one packed GEMM into
     [B, Li, 2D];
-  * the text decoder (post-LN BERT with a cross-attention block) ONE token per step: the new token's K|V
-    GEMM writes row t of the self-attention cache [B, Tmax, 2D] directly, the single query attends to
-    rows 0..t and to the Li image keys with kernels.attn_decode, and the vocabulary projection never
-    writes its logits: kernels.lm_head_argmax reads the tied embedding table once per step and returns
-    the token, kernels.greedy_select applies the stop / pad / forced-token rule and writes the token
-    where the next step's embedding kernel reads it. No token visits the host between steps, so the
-    whole unrolled loop (vision tower included) is one captured HIP graph per (batch, steps, precision).
-  * beam search: B images x nb beams are B * nb decoder rows that share the image's cross-attention K|V. A step
-    writes its fp32 logits, kernels.beam_select leaves the 2 nb best (score, beam, token) per image,
-    kernels.beam_update does transformers' bookkeeping on device state (running and finished hypotheses, the
-    early-stop heuristic, the next token and the parent row of every beam) and kernels.beam_reorder gathers the
-    self-attention caches by parent into a second set of buffers: still no host decision between steps and one
-    captured graph per (batch, steps, precision, num_beams, length_penalty, early_stopping).
+  * the text decoder (post-LN BERT with a cross-attention block) ONE token per step, one loop for all modes (_run):
+    the new token's K|V GEMM writes row t of the self-attention cache [Bp, Tmax, 2D] directly, the single query
+    attends to rows 0..t and to the Li image keys with kernels.attn_decode (_hidden), and the mode selects the next
+    token and writes it where the next step's embedding kernel reads it. Greedy (_Greedy): kernels.lm_head_argmax
+    reads the tied embedding table once and returns the token without writing logits, kernels.greedy_select applies
+    the stop / pad / forced-token rule. Sampling (_Sample, n rows per image): the LM head writes fp32 logits,
+    kernels.sample_select draws, then the greedy rule. Beam search (_Beams, nb rows per image): kernels.beam_select
+    leaves the 2 nb best (score, beam, token) per image, kernels.beam_update does transformers' bookkeeping on
+    device state and kernels.beam_reorder gathers the caches by parent into a second set. An image's rows share its
+    cross-attention K|V. No token visits the host between steps, so the unrolled loop (vision tower included) is
+    one captured HIP graph per state (_state: mode and parameters, batch, steps, precision), replayed by _decode.
   * the caption loss (forward(labels=)) shares no code with generation: ONE pass of the decoder over all T
     positions with no K|V cache — embeddings, per layer the packed Q|K|V GEMM, attn_fwd under a causal additive
     bias [H, T, T] and the key-padding bias, output projection + LayerNorm, cross-attention of the text rows over
@@ -143,6 +141,210 @@ def _attn_block(D, kv_in, eps):
     a.output.dense = nn.Linear(D, D)
     a.output.LayerNorm = nn.LayerNorm(D, eps=eps)
     return a
+
+
+class _Greedy:
+    """What a decoding mode adds to the one state builder, loop and driver of BlipForConditionalGeneration (_state,
+    _run, _decode), here for greedy decoding: its state key and buffers, the state before the first step, the
+    selection of step t (from the LM head to the write of seq[t + 1]), when an eager run may stop, and the result.
+    `m` is the model, `st` the state, `g` the LM head's input of the step (_hidden)."""
+    rows = 1         # decoder rows per image
+    min_new = 0      # the fewest max_new_tokens: a prompt of two ids with nothing to generate is accepted
+    wide_ok = False  # more than 32 rows on the wide LM head: generate's greedy calls only
+
+    def __init__(self, wide_ok=False):
+        self.wide_ok = wide_ok
+
+    def key(self, B, steps, dt, dev):
+        return (B, steps, dt, dev)
+
+    def buffers(self, m, st, dev):
+        st["forced"] = torch.zeros(st["steps"] + 1, st["R"], dtype=torch.int64, device=dev)
+        st["finished"] = torch.zeros(st["R"], dtype=torch.int32, device=dev)
+
+    def begin(self, m, st, prompt):
+        """prompt: the ids [P] shared by all rows, or [P, rows] (forward_logits)"""
+        ids = torch.as_tensor(prompt, dtype=torch.int64, device=st["seq"].device)
+        st["forced"].zero_()
+        st["forced"][:len(ids)] = ids.view(len(ids), -1)
+        st["seq"].zero_()
+        st["seq"][0, :st["R"]].copy_(st["forced"][0])
+        st["finished"].zero_()
+
+    def cache(self, st, t, n_forced):
+        return st["self_kv"]
+
+    def select(self, m, sc, st, g, t, n_forced, logits=None):
+        """the fused argmax, then the stop / pad / forced-token rule. logits (forward_logits): where the LM head also
+        writes the step's fp32 logits; the last step then selects nothing"""
+        tc = m.config.text
+        R, P, forced = st["R"], sc.P, t < n_forced
+        # more than 32 rows: the wide LM head, the narrow kernel's body over 32-row tiles
+        lm_head = K.lm_head_argmax_wide if st["wide"] else K.lm_head_argmax
+        if st.get("proc") is None or logits is not None:
+            # (a forced step discards this argmax: wasted work, and a launch less is another captured graph)
+            lm_head(g[:R], sc.w(WORD), P[HEAD + "bias"], out=st["argmax"], logits=logits, workspace=st["lm_ws"])
+        elif not forced:
+            # logits processors: the LM head stores its fp32 logits, the edits run on them, and the argmax is taken
+            # of the edited row (a fix-up of the fused argmax would not do: were the raw winner an edited column,
+            # the best unedited one would be unknown). A forced step needs neither: its token is the prompt's.
+            lm_head(g[:R], sc.w(WORD), P[HEAD + "bias"], out=st["argmax"], logits=st["logits"], workspace=st["lm_ws"])
+            m._edit(st, st["logits"], st["seq"], "steps", t)
+            K.row_argmax(st["logits"], out=st["argmax"])
+        if logits is None or t + 1 < st["steps"]:
+            K.greedy_select(st["argmax"], st["finished"], tc.sep_token_id, tc.pad_token_id, st["seq"][t + 1, :R],
+                            forced=st["forced"][t + 1] if forced else None)
+
+    def stop(self, st, t, n_forced):
+        return t >= n_forced and bool(st["finished"].all())
+
+    def result(self, m, st, n_prompt, max_new_tokens, ran):
+        """int64 [rows, P + n] ids. ran: the steps an eager run took; None after a replay, which ran them all: the
+        ids are then trimmed on the host to where the last row stopped"""
+        R = st["R"]
+        if ran is not None:
+            return st["seq"][:ran + 1, :R].t().contiguous().cpu()
+        seq = st["seq"][:, :R].t().cpu()
+        done = seq[:, n_prompt:] == m.config.text.sep_token_id
+        first = torch.where(done.any(1), done.int().argmax(1) + 1, torch.tensor(max_new_tokens))
+        return seq[:, :n_prompt + int(first.max())].contiguous()
+
+
+class _Sample(_Greedy):
+    """sampling: the greedy mode with the argmax replaced, n rows per image"""
+    min_new = 1
+
+    def __init__(self, m, n, temperature, top_k, top_p, seed, row_offset):
+        if row_offset < 0:
+            raise ValueError(f"row_offset must be >= 0, got {row_offset}")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        self.seed = m.sample_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.rows, self.temperature, self.top_k, self.top_p, self.row_offset = n, temperature, top_k, top_p, row_offset
+
+    def key(self, B, steps, dt, dev):
+        return ("sample", B, self.rows, steps, dt, dev, self.temperature, self.top_k, self.top_p)
+
+    def buffers(self, m, st, dev):
+        """beside the greedy ones: the fp32 logits of one step, the sampled tokens and the {seed, row offset} the
+        selection reads on the device"""
+        super().buffers(m, st, dev)
+        R, V_ = st["R"], m.config.text.vocab_size
+        st["token"] = torch.zeros(R, dtype=torch.int64, device=dev)
+        st["ctl"] = torch.zeros(2, dtype=torch.int64, device=dev)
+        st["logits"] = torch.zeros(R, V_, device=dev)
+        st["smp_ws"] = torch.empty(K.sample_select_workspace_bytes(R, V_), dtype=torch.uint8, device=dev)
+
+    def begin(self, m, st, prompt):
+        super().begin(m, st, prompt)
+        seed = self.seed - (1 << 64) if self.seed >= (1 << 63) else self.seed
+        st["ctl"].copy_(torch.tensor([seed, self.row_offset], dtype=torch.int64))
+
+    def select(self, m, sc, st, g, t, n_forced, logits=None):
+        """the LM head writes the fp32 logits, sample_select draws the row's token from them, and the unchanged
+        greedy rule applies forced / finished / pad / eos. A forced step needs no logits: its token is the prompt's."""
+        tc = m.config.text
+        R, forced = st["R"], t < n_forced
+        if not forced:
+            K.lm_head_argmax(g[:R], sc.w(WORD), sc.P[HEAD + "bias"], out=st["argmax"], logits=st["logits"],
+                             workspace=st["lm_ws"])
+            if st.get("proc") is not None:  # the processors come before the warpers, as in transformers
+                m._edit(st, st["logits"], st["seq"], "steps", t)
+            K.sample_select(st["logits"], self.temperature, self.top_k, self.top_p, st["ctl"], t, out=st["token"],
+                            workspace=st["smp_ws"])
+        K.greedy_select(st["token"], st["finished"], tc.sep_token_id, tc.pad_token_id, st["seq"][t + 1, :R],
+                        forced=st["forced"][t + 1] if forced else None)
+
+
+class _Beams:
+    """beam search: nb rows per image, the search state of csrc/beam.hip, and two sets of self-attention caches
+    between which the reorder gathers by parent"""
+    min_new = 1
+    wide_ok = False
+
+    def __init__(self, nb, lp, early):
+        self.rows, self.lp, self.early = nb, lp, early
+
+    def key(self, B, steps, dt, dev):
+        return (B, steps, dt, dev, self.rows, self.lp, self.early)
+
+    def buffers(self, m, st, dev):
+        B, R, nb, T_, V_ = st["B"], st["R"], self.rows, st["steps"] + 1, m.config.text.vocab_size
+        i32 = dict(dtype=torch.int32, device=dev)
+        st["kv"] = [st["self_kv"], [torch.zeros_like(c) for c in st["self_kv"]]]
+        st["kv_table"] = [K.ptr_table(st["kv"][0]), K.ptr_table(st["kv"][1])]
+        st["logits"] = torch.zeros(R, V_, device=dev)
+        st["cand"] = (torch.zeros(B, 2 * nb, device=dev), torch.zeros(B, 2 * nb, **i32), torch.zeros(B, 2 * nb, **i32))
+        st["beam"] = dict(run_score=torch.zeros(B, nb, device=dev), fin_score=torch.zeros(B, nb, device=dev),
+                          fin_flag=torch.zeros(B, nb, **i32), fin_len=torch.zeros(B, nb, **i32),
+                          run_seq=torch.zeros(B, nb, T_, **i32), fin_seq=torch.zeros(B, nb, T_, **i32),
+                          flags=torch.zeros(B, 4, **i32), parent=torch.zeros(R, **i32))
+        st["sel_ws"] = torch.empty(K.beam_select_workspace_bytes(B, nb, V_), dtype=torch.uint8, device=dev)
+
+    def begin(self, m, st, prompt):
+        """the state before the first step (transformers' step 3): every beam holds the prompt, which the forced
+        steps embed token by token; running scores [0, -1e9, ...]; nothing finished"""
+        tc = m.config.text
+        bs, R = st["beam"], st["R"]
+        ids = torch.tensor(prompt, dtype=torch.int64, device=st["seq"].device)
+        st["seq"].zero_()
+        st["seq"][:len(prompt), :R] = ids[:, None]
+        bs["run_seq"].fill_(tc.pad_token_id or tc.sep_token_id)  # transformers: `pad_token_id or eos_token_id[0]`
+        bs["run_seq"][:, :, :len(prompt)] = ids.int()
+        bs["fin_seq"].copy_(bs["run_seq"])
+        bs["run_score"].fill_(-1.0e9)
+        bs["run_score"][:, 0] = 0.0
+        bs["fin_score"].fill_(-1.0e9)
+        bs["fin_flag"].zero_()
+        bs["fin_len"].zero_()
+        bs["flags"].zero_()
+        bs["flags"][:, 0] = 1
+        bs["parent"].copy_(torch.arange(R, dtype=torch.int32, device=bs["parent"].device))
+
+    def cache(self, st, t, n_forced):
+        return st["kv"][max(t - n_forced, 0) & 1]  # every free step but the last gathers into the other set
+
+    def select(self, m, sc, st, g, t, n_forced, logits=None):
+        """A forced step only feeds the decoder: its next token is the prompt's, already in st['seq']. A free step
+        writes the fp32 logits, selects the 2 nb candidates of every image, updates the search state (which writes
+        the next tokens and the parent rows) and gathers the caches by parent into the other set."""
+        if t < n_forced:
+            return
+        tc = m.config.text
+        R, nb, steps = st["R"], self.rows, st["steps"]
+        K.lm_head_argmax(g[:R], sc.w(WORD), sc.P[HEAD + "bias"], out=st["argmax"], logits=st["logits"],
+                         workspace=st["lm_ws"])
+        if st.get("proc") is None:
+            K.beam_select(st["logits"], st["beam"]["run_score"].view(-1), nb, out=st["cand"], workspace=st["sel_ws"])
+        else:
+            # transformers hands log_softmax(logits) of every running beam to the processors and adds the running
+            # score afterwards: normalise once (over the unprocessed row), edit from the beam's own sequence as
+            # the last update left it, select without a second normalisation
+            K.row_log_softmax(st["logits"], workspace=st["sel_ws"])
+            m._edit(st, st["logits"], st["beam"]["run_seq"].view(R, steps + 1), "rows", t)
+            K.beam_select_logprobs(st["logits"], st["beam"]["run_score"].view(-1), nb, out=st["cand"],
+                                   workspace=st["sel_ws"])
+        K.beam_update(st["cand"], st["beam"], t, n_forced, t + 1 == steps, tc.sep_token_id, self.lp, self.early,
+                      st["seq"][t + 1, :R])
+        if t + 1 < steps:
+            cur = (t - n_forced) & 1
+            K.beam_reorder(st["kv"][cur], st["kv"][1 - cur], st["kv_table"][cur], st["kv_table"][1 - cur],
+                           st["beam"]["parent"], R, t + 1)
+
+    def stop(self, st, t, n_forced):
+        """transformers' loop condition, from one host read of the per-image flags: an eager run leaves once
+        transformers would (the remaining steps change nothing: every update of an image that cannot improve is
+        masked)"""
+        if t < n_forced:
+            return False
+        f = st["beam"]["flags"].cpu().bool()
+        return not (bool(f[:, 0].any()) and not (self.early and bool(f[:, 1].all())) and not bool(f[:, 2].all()))
+
+    def result(self, m, st, n_prompt, max_new_tokens, ran):
+        bs = st["beam"]
+        n = int(bs["fin_len"][:, 0].max())  # transformers counts the entries of the chosen hypotheses' beam trail
+        m.sequences_scores = bs["fin_score"][:, 0].clone()
+        return bs["fin_seq"][:, 0, :n_prompt + n].long().cpu().contiguous()
 
 
 class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
@@ -323,52 +525,54 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
                          eos=self.config.text.sep_token_id, suppress=st["suppress"] if sup else None,
                          n_suppress=len(sup), history_layout=layout)
 
-    def _state(self, B, steps, dev, proc=None, wide_ok=False):
-        """the device buffers of one (batch, steps, precision): static inputs, caches, workspaces; with logits
-        processors also the fp32 logits of one step and the suppress list. wide_ok (greedy generate): more than 32
-        rows get the wide LM head's workspace; such a state is large (its graph holds the cross-attention K|V of
-        every row), so the cached states and their graphs go before its buffers are allocated"""
-        key = (B, steps, self.compute_dtype, str(dev)) + self._proc_key(proc)
+    def _state(self, mode, B, steps, dev, proc=None):
+        """the device buffers of one (mode and its parameters, batch, steps, precision): static inputs, caches and
+        workspaces for B * mode.rows decoder rows, then what the mode adds (mode.buffers); with logits processors also
+        the suppress list and, where the mode has none, the fp32 logits of one step. Where the mode allows it (greedy
+        generate) more than 32 rows get the wide LM head's workspace; such a state is large (its graph holds the
+        cross-attention K|V of every row), so the cached states and their graphs go before its buffers are allocated"""
+        dt = self.compute_dtype
+        key = mode.key(B, steps, dt, str(dev)) + self._proc_key(proc)
         st = self._states.get(key)
         if st is not None:
             return st
-        wide = bool(wide_ok) and B > 32
+        R = B * mode.rows
+        wide = bool(mode.wide_ok) and R > 32
         if wide:
             self._states.clear()
         vc, tc = self.config.vision, self.config.text
-        dt, E, H = self.compute_dtype, tc.hidden_size, tc.num_attention_heads
+        E, H = tc.hidden_size, tc.num_attention_heads
         Li = (vc.image_size // vc.patch_size) ** 2 + 1
         # mmfd_gemm runs products of fewer than 16 rows on its scalar path: the decoder's activations carry
         # at least 16 rows (the padding rows embed token 0 and are never selected, attended across or read)
-        Bp = max(B, 16)
+        Bp = max(R, 16)
         st = dict(
-            B=B, Bp=Bp, steps=steps, Li=Li,
+            B=B, R=R, Bp=Bp, steps=steps, Li=Li, wide=wide,
             px=torch.zeros(B, vc.num_channels, vc.image_size, vc.image_size, device=dev),
             # token ids step-major: row t is what step t embeds (contiguous), row t + 1 what it selects
             seq=torch.zeros(steps + 1, Bp, dtype=torch.int64, device=dev),
-            forced=torch.zeros(steps + 1, B, dtype=torch.int64, device=dev),
             pos=torch.arange(steps + 1, dtype=torch.int64, device=dev)[:, None].expand(steps + 1, Bp).contiguous(),
-            finished=torch.zeros(B, dtype=torch.int32, device=dev),
-            argmax=torch.zeros(B, dtype=torch.int64, device=dev),
+            argmax=torch.zeros(R, dtype=torch.int64, device=dev),
             self_kv=[torch.zeros(Bp, steps, 2 * E, device=dev, dtype=dt) for _ in range(tc.num_hidden_layers)],
-            cross_o=torch.zeros(Bp, E, device=dev, dtype=dt),  # cross-attention output: rows >= B stay 0
+            cross_o=torch.zeros(Bp, E, device=dev, dtype=dt),  # cross-attention output: rows >= R stay 0
             graph=None, sig=None, n_forced=-1)
         need = max(K.lib().mmfd_attn_decode_workspace_bytes(B, H, E // H, Li),
+                   K.lib().mmfd_attn_decode_workspace_bytes(R, H, E // H, Li),
                    K.lib().mmfd_attn_decode_workspace_bytes(Bp, H, E // H, steps), 16)
         st["attn_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
-        st["wide"] = wide
         if wide:
-            need = K.lib().mmfd_lm_head_argmax_wide_workspace_bytes(K.dtype_code(dt), B, tc.vocab_size, E)
+            need = K.lib().mmfd_lm_head_argmax_wide_workspace_bytes(K.dtype_code(dt), R, tc.vocab_size, E)
             if need <= 0:
                 raise ValueError(f"mmfd BLIP: the wide LM head kernel takes at most 256 rows and widths up to 1024, "
                                  f"got batch {B}, width {E}")
         else:
-            need = K.lib().mmfd_lm_head_argmax_workspace_bytes(K.dtype_code(dt), B, tc.vocab_size, E)
+            need = K.lib().mmfd_lm_head_argmax_workspace_bytes(K.dtype_code(dt), R, tc.vocab_size, E)
             if need <= 0:
                 raise ValueError(f"mmfd BLIP: the LM head kernel takes at most 32 rows and widths up to 1024 (fp32) / "
-                                 f"2048 (bf16), got batch {B}, width {E}")
+                                 f"2048 (bf16), got {R} rows, width {E}")
         st["lm_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
-        self._proc_buffers(st, proc, B, dev)
+        mode.buffers(self, st, dev)
+        self._proc_buffers(st, proc, R, dev)
         if len(self._states) >= 8:
             self._states.clear()
         self._states[key] = st
@@ -449,40 +653,20 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
         g, _, _ = Bk.layernorm(sc, g, HEAD + "transform.LayerNorm", eps)
         return g
 
-    def _step(self, sc, st, cross, t, forced, logits=None, select=True):
-        """decoder step t: embeds st['seq'][t] at position t, appends its K|V to the self cache, and
-        (select) writes the next token to st['seq'][t + 1]"""
-        tc = self.config.text
-        B, P = st["B"], sc.P
-        g = self._hidden(sc, st, cross, t, st["self_kv"])
-        # more than 32 rows (greedy generate only): the wide LM head, the narrow kernel's body over 32-row tiles
-        lm_head = K.lm_head_argmax_wide if st.get("wide") else K.lm_head_argmax
-        if st.get("proc") is None or logits is not None:
-            lm_head(g[:B], sc.w(WORD), P[HEAD + "bias"], out=st["argmax"], logits=logits, workspace=st["lm_ws"])
-        elif not forced:
-            # logits processors: the LM head stores its fp32 logits, the edits run on them, and the argmax is taken
-            # of the edited row (a fix-up of the fused argmax would not do: were the raw winner an edited column,
-            # the best unedited one would be unknown). A forced step needs neither: its token is the prompt's.
-            lm_head(g[:B], sc.w(WORD), P[HEAD + "bias"], out=st["argmax"], logits=st["logits"], workspace=st["lm_ws"])
-            self._edit(st, st["logits"], st["seq"], "steps", t)
-            K.row_argmax(st["logits"], out=st["argmax"])
-        if select:
-            K.greedy_select(st["argmax"], st["finished"], tc.sep_token_id, tc.pad_token_id, st["seq"][t + 1, :B],
-                            forced=st["forced"][t + 1] if forced else None)
-
-    def _run(self, st, n_forced, logits=None):
-        """vision tower, cross K|V and every step on the state's static buffers; steps t < n_forced take
-        their next token from st['forced'][t + 1]"""
-        sc, _ = self._ctx()
+    def _run(self, st, n_forced, eager=False, logits=None, sc=None):
+        """vision tower, cross K|V, then per step the decoder body and the mode's selection, all on the state's static
+        buffers; steps t < n_forced take their next token from the prompt. eager: ask the mode after every step
+        whether to stop (one host read). Returns the steps run. logits: forward_logits' sink [steps, B, V]. sc: the
+        caller's context, so that an eager call builds one and not two"""
+        mode = st["mode"]
+        sc = sc or self._ctx()[0]
         cross = self._cross_kv(sc, self._vision(sc, st["px"]))
         for t in range(st["steps"]):
-            self._step(sc, st, cross, t, forced=t < n_forced, logits=None if logits is None else logits[t],
-                       select=logits is None or t + 1 < st["steps"])
-
-    def _begin(self, st, first_tokens):
-        st["seq"].zero_()
-        st["seq"][0, :st["B"]].copy_(first_tokens)
-        st["finished"].zero_()
+            g = self._hidden(sc, st, cross, t, mode.cache(st, t, n_forced), mode.rows)
+            mode.select(self, sc, st, g, t, n_forced, None if logits is None else logits[t])
+            if eager and mode.stop(st, t, n_forced):
+                return t + 1
+        return st["steps"]
 
     def _prompt(self, input_ids):
         """the shared prompt as a list of ids starting with bos (transformers' generate: input_ids[:, 0] = bos
@@ -574,307 +758,54 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
         px = pixel_values.to(dev).float().contiguous()
         prompt = self._prompt(input_ids)
         if do_sample:
-            return self._generate_sample(sc, dev, px, prompt, int(max_new_tokens), bool(use_graph), int(n_ret),
-                                         float(temperature), int(top_k), float(top_p), seed, int(row_offset), proc)
-        if num_beams > 1:
-            return self._generate_beams(sc, dev, px, prompt, int(max_new_tokens), bool(use_graph), int(num_beams),
-                                        float(length_penalty), bool(early_stopping), proc)
-        if B > self.MAX_GREEDY_ROWS:
-            raise ValueError(f"greedy decoding takes at most {self.MAX_GREEDY_ROWS} rows per call, got batch {B}")
+            mode = _Sample(self, int(n_ret), float(temperature), int(top_k), float(top_p), seed, int(row_offset))
+        elif num_beams > 1:
+            mode = _Beams(int(num_beams), float(length_penalty), bool(early_stopping))
+        else:
+            if B > self.MAX_GREEDY_ROWS:
+                raise ValueError(f"greedy decoding takes at most {self.MAX_GREEDY_ROWS} rows per call, got batch {B}")
+            mode = _Greedy(wide_ok=True)
+        return self._decode(mode, sc, dev, px, prompt, int(max_new_tokens), bool(use_graph), proc)
+
+    def _decode(self, mode, sc, dev, px, prompt, max_new_tokens, use_graph, proc):
+        """the driver of every mode: the state, this call's inputs, then one replay of the captured graph of all
+        steps (captured first where the state has none, or the weights or the prompt's length changed since) or an
+        eager run that stops once the mode says so"""
+        tc = self.config.text
         n_forced = len(prompt) - 1
-        steps = n_forced + int(max_new_tokens)
-        if steps < 1 or steps + 1 > tc.max_position_embeddings:
+        steps = n_forced + max_new_tokens
+        if max_new_tokens < mode.min_new or steps < 1 or steps + 1 > tc.max_position_embeddings:
             raise ValueError(f"prompt ({len(prompt)}) + max_new_tokens ({max_new_tokens}) must lie in "
                              f"[2, {tc.max_position_embeddings}]")
-        st = self._state(B, steps, dev, proc, wide_ok=True)
+        st = self._state(mode, px.shape[0], steps, dev, proc)
         if tuple(px.shape) != tuple(st["px"].shape):
             raise ValueError(f"pixel_values must be {tuple(st['px'].shape)}, got {tuple(px.shape)}")
         st["px"].copy_(px)
-        st["forced"].zero_()
-        st["forced"][:len(prompt)] = torch.tensor(prompt, dtype=torch.int64, device=dev)[:, None]
-        self._begin(st, st["forced"][0])
+        st["mode"] = mode  # (this call's: the seed and the row offset of a sampling call are not in the state's key)
+        mode.begin(self, st, prompt)
         self._proc_begin(st, proc, len(prompt))
-        if use_graph:
+        ran = None
+        if not use_graph:
+            ran = self._run(st, n_forced, eager=True, sc=sc)
+        else:
             if st["graph"] is None or st["sig"] != self._signature() or st["n_forced"] != n_forced:
                 self._capture(st, n_forced, dev)
-                self._begin(st, st["forced"][0])
+                mode.begin(self, st, prompt)
             st["graph"].replay()
-            seq = st["seq"][:, :B].t().cpu()
-            done = seq[:, n_forced + 1:] == tc.sep_token_id
-            first = torch.where(done.any(1), done.int().argmax(1) + 1, torch.tensor(int(max_new_tokens)))
-            return seq[:, :n_forced + 1 + int(first.max())].contiguous()
-        cross = self._cross_kv(sc, self._vision(sc, st["px"]))
-        n = steps
-        for t in range(steps):
-            self._step(sc, st, cross, t, forced=t < n_forced)
-            if t >= n_forced and bool(st["finished"].all()):
-                n = t + 1
-                break
-        return st["seq"][:n + 1, :B].t().contiguous().cpu()
+        return mode.result(self, st, len(prompt), max_new_tokens, ran)
 
-    def _capture(self, st, n_forced, dev, run=None):
-        run = run or self._run
+    def _capture(self, st, n_forced, dev):
         st["graph"] = None
         st["sig"], st["n_forced"] = self._signature(), n_forced
         s = torch.cuda.Stream(device=dev)
         s.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(s):
-            run(st, n_forced)  # warm up: weight shadows, packed biases, kernel attributes
+            self._run(st, n_forced)  # warm up: weight shadows, packed biases, kernel attributes
         torch.cuda.current_stream(dev).wait_stream(s)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            run(st, n_forced)
+            self._run(st, n_forced)
         st["graph"] = g
-
-    # ---- sampling ------------------------------------------------------------------------------------
-    def _sample_state(self, B, steps, dev, n, temperature, top_k, top_p, proc=None):
-        """the device buffers of one (batch, samples per image, steps, precision, sampling parameters): what _state
-        holds for B * n rows, the fp32 logits of one step, the sampled tokens and the {seed, row offset} the
-        selection reads on the device"""
-        key = ("sample", B, n, steps, self.compute_dtype, str(dev), temperature, top_k, top_p) + self._proc_key(proc)
-        st = self._states.get(key)
-        if st is not None:
-            return st
-        vc, tc = self.config.vision, self.config.text
-        dt, E, H = self.compute_dtype, tc.hidden_size, tc.num_attention_heads
-        Li = (vc.image_size // vc.patch_size) ** 2 + 1
-        R = B * n
-        Bp = max(R, 16)
-        st = dict(
-            B=B, Bp=Bp, R=R, n=n, steps=steps, Li=Li, temperature=temperature, top_k=top_k, top_p=top_p,
-            px=torch.zeros(B, vc.num_channels, vc.image_size, vc.image_size, device=dev),
-            seq=torch.zeros(steps + 1, Bp, dtype=torch.int64, device=dev),
-            forced=torch.zeros(steps + 1, R, dtype=torch.int64, device=dev),
-            pos=torch.arange(steps + 1, dtype=torch.int64, device=dev)[:, None].expand(steps + 1, Bp).contiguous(),
-            finished=torch.zeros(R, dtype=torch.int32, device=dev),
-            argmax=torch.zeros(R, dtype=torch.int64, device=dev),
-            token=torch.zeros(R, dtype=torch.int64, device=dev),
-            ctl=torch.zeros(2, dtype=torch.int64, device=dev),
-            self_kv=[torch.zeros(Bp, steps, 2 * E, device=dev, dtype=dt) for _ in range(tc.num_hidden_layers)],
-            cross_o=torch.zeros(Bp, E, device=dev, dtype=dt),
-            logits=torch.zeros(R, tc.vocab_size, device=dev),
-            graph=None, sig=None, n_forced=-1)
-        need = max(K.lib().mmfd_attn_decode_workspace_bytes(B, H, E // H, Li),
-                   K.lib().mmfd_attn_decode_workspace_bytes(R, H, E // H, Li),
-                   K.lib().mmfd_attn_decode_workspace_bytes(Bp, H, E // H, steps), 16)
-        st["attn_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
-        need = K.lib().mmfd_lm_head_argmax_workspace_bytes(K.dtype_code(dt), R, tc.vocab_size, E)
-        if need <= 0:
-            raise ValueError(f"mmfd BLIP: the LM head kernel takes at most 32 rows and widths up to 1024 (fp32) / 2048 "
-                             f"(bf16), got {R} rows, width {E}")
-        st["lm_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
-        st["smp_ws"] = torch.empty(K.sample_select_workspace_bytes(R, tc.vocab_size), dtype=torch.uint8, device=dev)
-        self._proc_buffers(st, proc, R, dev)
-        if len(self._states) >= 8:
-            self._states.clear()
-        self._states[key] = st
-        return st
-
-    def _sample_step(self, sc, st, cross, t, forced):
-        """the greedy step with the argmax replaced: the LM head writes the fp32 logits, sample_select draws the
-        row's token from them, and the unchanged greedy rule applies forced / finished / pad / eos. A forced step
-        needs no logits: its token is the prompt's."""
-        tc = self.config.text
-        R = st["R"]
-        g = self._hidden(sc, st, cross, t, st["self_kv"], st["n"])
-        if not forced:
-            K.lm_head_argmax(g[:R], sc.w(WORD), sc.P[HEAD + "bias"], out=st["argmax"], logits=st["logits"],
-                             workspace=st["lm_ws"])
-            if st.get("proc") is not None:  # the processors come before the warpers, as in transformers
-                self._edit(st, st["logits"], st["seq"], "steps", t)
-            K.sample_select(st["logits"], st["temperature"], st["top_k"], st["top_p"], st["ctl"], t, out=st["token"],
-                            workspace=st["smp_ws"])
-        K.greedy_select(st["token"], st["finished"], tc.sep_token_id, tc.pad_token_id, st["seq"][t + 1, :R],
-                        forced=st["forced"][t + 1] if forced else None)
-
-    def _sample_run(self, st, n_forced):
-        sc, _ = self._ctx()
-        cross = self._cross_kv(sc, self._vision(sc, st["px"]))
-        for t in range(st["steps"]):
-            self._sample_step(sc, st, cross, t, forced=t < n_forced)
-
-    def _sample_begin(self, st, seed, row_offset):
-        st["seq"].zero_()
-        st["seq"][0, :st["R"]].copy_(st["forced"][0])
-        st["finished"].zero_()
-        st["ctl"].copy_(torch.tensor([seed - (1 << 64) if seed >= (1 << 63) else seed, row_offset], dtype=torch.int64))
-
-    def _generate_sample(self, sc, dev, px, prompt, max_new_tokens, use_graph, n, temperature, top_k, top_p, seed,
-                         row_offset, proc=None):
-        tc = self.config.text
-        B = px.shape[0]
-        n_forced = len(prompt) - 1
-        steps = n_forced + max_new_tokens
-        if max_new_tokens < 1 or steps + 1 > tc.max_position_embeddings:
-            raise ValueError(f"prompt ({len(prompt)}) + max_new_tokens ({max_new_tokens}) must lie in "
-                             f"[2, {tc.max_position_embeddings}]")
-        if row_offset < 0:
-            raise ValueError(f"row_offset must be >= 0, got {row_offset}")
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
-        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        self.sample_seed = seed
-        st = self._sample_state(B, steps, dev, n, temperature, top_k, top_p, proc)
-        if tuple(px.shape) != tuple(st["px"].shape):
-            raise ValueError(f"pixel_values must be {tuple(st['px'].shape)}, got {tuple(px.shape)}")
-        st["px"].copy_(px)
-        st["forced"].zero_()
-        st["forced"][:len(prompt)] = torch.tensor(prompt, dtype=torch.int64, device=dev)[:, None]
-        self._sample_begin(st, seed, row_offset)
-        self._proc_begin(st, proc, len(prompt))
-        R = st["R"]
-        if use_graph:
-            if st["graph"] is None or st["sig"] != self._signature() or st["n_forced"] != n_forced:
-                self._capture(st, n_forced, dev, run=self._sample_run)
-                self._sample_begin(st, seed, row_offset)
-            st["graph"].replay()
-            seq = st["seq"][:, :R].t().cpu()
-            done = seq[:, n_forced + 1:] == tc.sep_token_id
-            first = torch.where(done.any(1), done.int().argmax(1) + 1, torch.tensor(max_new_tokens))
-            return seq[:, :n_forced + 1 + int(first.max())].contiguous()
-        cross = self._cross_kv(sc, self._vision(sc, st["px"]))
-        last = steps
-        for t in range(steps):
-            self._sample_step(sc, st, cross, t, forced=t < n_forced)
-            if t >= n_forced and bool(st["finished"].all()):
-                last = t + 1
-                break
-        return st["seq"][:last + 1, :R].t().contiguous().cpu()
-
-    # ---- beam search ---------------------------------------------------------------------------------
-    def _beam_state(self, B, steps, dev, nb, lp, early, proc=None):
-        """the device buffers of one (batch, steps, precision, beam parameters): what _state holds for B * nb rows,
-        a second set of self-attention caches (the reorder gathers from one into the other), the fp32 logits of
-        one step and the search state of csrc/beam.hip"""
-        key = (B, steps, self.compute_dtype, str(dev), nb, lp, early) + self._proc_key(proc)
-        st = self._states.get(key)
-        if st is not None:
-            return st
-        vc, tc = self.config.vision, self.config.text
-        dt, E, H, L = self.compute_dtype, tc.hidden_size, tc.num_attention_heads, tc.num_hidden_layers
-        Li = (vc.image_size // vc.patch_size) ** 2 + 1
-        R, T = B * nb, steps + 1
-        Bp = max(R, 16)
-        i32 = dict(dtype=torch.int32, device=dev)
-        kv = [[torch.zeros(Bp, steps, 2 * E, device=dev, dtype=dt) for _ in range(L)] for _ in range(2)]
-        st = dict(
-            B=B, Bp=Bp, R=R, nb=nb, lp=lp, early=early, steps=steps, Li=Li,
-            px=torch.zeros(B, vc.num_channels, vc.image_size, vc.image_size, device=dev),
-            seq=torch.zeros(T, Bp, dtype=torch.int64, device=dev),
-            pos=torch.arange(T, dtype=torch.int64, device=dev)[:, None].expand(T, Bp).contiguous(),
-            argmax=torch.zeros(R, dtype=torch.int64, device=dev),
-            kv=kv, kv_table=[K.ptr_table(kv[0]), K.ptr_table(kv[1])],
-            cross_o=torch.zeros(Bp, E, device=dev, dtype=dt),
-            logits=torch.zeros(R, tc.vocab_size, device=dev),
-            cand=(torch.zeros(B, 2 * nb, device=dev), torch.zeros(B, 2 * nb, **i32), torch.zeros(B, 2 * nb, **i32)),
-            beam=dict(run_score=torch.zeros(B, nb, device=dev), fin_score=torch.zeros(B, nb, device=dev),
-                      fin_flag=torch.zeros(B, nb, **i32), fin_len=torch.zeros(B, nb, **i32),
-                      run_seq=torch.zeros(B, nb, T, **i32), fin_seq=torch.zeros(B, nb, T, **i32),
-                      flags=torch.zeros(B, 4, **i32), parent=torch.zeros(R, **i32)),
-            graph=None, sig=None, n_forced=-1)
-        need = max(K.lib().mmfd_attn_decode_workspace_bytes(B, H, E // H, Li),
-                   K.lib().mmfd_attn_decode_workspace_bytes(R, H, E // H, Li),
-                   K.lib().mmfd_attn_decode_workspace_bytes(Bp, H, E // H, steps), 16)
-        st["attn_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
-        need = K.lib().mmfd_lm_head_argmax_workspace_bytes(K.dtype_code(dt), R, tc.vocab_size, E)
-        if need <= 0:
-            raise ValueError(f"mmfd BLIP: the LM head kernel takes at most 32 rows and widths up to 1024 (fp32) / 2048 "
-                             f"(bf16), got {R} rows, width {E}")
-        st["lm_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
-        st["sel_ws"] = torch.empty(K.beam_select_workspace_bytes(B, nb, tc.vocab_size), dtype=torch.uint8, device=dev)
-        self._proc_buffers(st, proc, R, dev)
-        if len(self._states) >= 8:
-            self._states.clear()
-        self._states[key] = st
-        return st
-
-    def _beam_begin(self, st, prompt):
-        """the state before the first step (transformers' step 3): every beam holds the prompt, which the forced
-        steps embed token by token; running scores [0, -1e9, ...]; nothing finished"""
-        tc = self.config.text
-        bs, R = st["beam"], st["R"]
-        ids = torch.tensor(prompt, dtype=torch.int64, device=st["seq"].device)
-        st["seq"].zero_()
-        st["seq"][:len(prompt), :R] = ids[:, None]
-        bs["run_seq"].fill_(tc.pad_token_id or tc.sep_token_id)  # transformers: `pad_token_id or eos_token_id[0]`
-        bs["run_seq"][:, :, :len(prompt)] = ids.int()
-        bs["fin_seq"].copy_(bs["run_seq"])
-        bs["run_score"].fill_(-1.0e9)
-        bs["run_score"][:, 0] = 0.0
-        bs["fin_score"].fill_(-1.0e9)
-        bs["fin_flag"].zero_()
-        bs["fin_len"].zero_()
-        bs["flags"].zero_()
-        bs["flags"][:, 0] = 1
-        bs["parent"].copy_(torch.arange(R, dtype=torch.int32, device=bs["parent"].device))
-
-    def _beam_unfinished(self, st):
-        """transformers' loop condition, from one host read of the per-image flags"""
-        f = st["beam"]["flags"].cpu().bool()
-        return bool(f[:, 0].any()) and not (st["early"] and bool(f[:, 1].all())) and not bool(f[:, 2].all())
-
-    def _beam_run(self, st, n_forced, eager=False):
-        """vision tower, cross K|V and every step. A forced step only feeds the decoder: its next token is the
-        prompt's, already in st['seq']. A free step writes the fp32 logits, selects the 2 nb candidates of every
-        image, updates the search state (which writes the next tokens and the parent rows) and gathers the
-        caches by parent into the other set. eager: leave once transformers would (the remaining steps change
-        nothing: every update of an image that cannot improve is masked)."""
-        tc = self.config.text
-        sc, _ = self._ctx()
-        R, nb, steps = st["R"], st["nb"], st["steps"]
-        cross = self._cross_kv(sc, self._vision(sc, st["px"]))
-        cur = 0
-        for t in range(steps):
-            g = self._hidden(sc, st, cross, t, st["kv"][cur], nb)
-            if t < n_forced:
-                continue
-            K.lm_head_argmax(g[:R], sc.w(WORD), sc.P[HEAD + "bias"], out=st["argmax"], logits=st["logits"],
-                             workspace=st["lm_ws"])
-            if st.get("proc") is None:
-                K.beam_select(st["logits"], st["beam"]["run_score"].view(-1), nb, out=st["cand"],
-                              workspace=st["sel_ws"])
-            else:
-                # transformers hands log_softmax(logits) of every running beam to the processors and adds the running
-                # score afterwards: normalise once (over the unprocessed row), edit from the beam's own sequence as
-                # the last update left it, select without a second normalisation
-                K.row_log_softmax(st["logits"], workspace=st["sel_ws"])
-                self._edit(st, st["logits"], st["beam"]["run_seq"].view(R, steps + 1), "rows", t)
-                K.beam_select_logprobs(st["logits"], st["beam"]["run_score"].view(-1), nb, out=st["cand"],
-                                       workspace=st["sel_ws"])
-            K.beam_update(st["cand"], st["beam"], t, n_forced, t + 1 == steps, tc.sep_token_id, st["lp"], st["early"],
-                          st["seq"][t + 1, :R])
-            if t + 1 < steps:
-                K.beam_reorder(st["kv"][cur], st["kv"][1 - cur], st["kv_table"][cur], st["kv_table"][1 - cur],
-                               st["beam"]["parent"], R, t + 1)
-                cur = 1 - cur
-            if eager and not self._beam_unfinished(st):
-                break
-
-    def _generate_beams(self, sc, dev, px, prompt, max_new_tokens, use_graph, nb, lp, early, proc=None):
-        tc = self.config.text
-        B = px.shape[0]
-        n_forced = len(prompt) - 1
-        steps = n_forced + max_new_tokens
-        if max_new_tokens < 1 or steps + 1 > tc.max_position_embeddings:
-            raise ValueError(f"prompt ({len(prompt)}) + max_new_tokens ({max_new_tokens}) must lie in "
-                             f"[2, {tc.max_position_embeddings}]")
-        st = self._beam_state(B, steps, dev, nb, lp, early, proc)
-        if tuple(px.shape) != tuple(st["px"].shape):
-            raise ValueError(f"pixel_values must be {tuple(st['px'].shape)}, got {tuple(px.shape)}")
-        st["px"].copy_(px)
-        self._beam_begin(st, prompt)
-        self._proc_begin(st, proc, len(prompt))
-        if use_graph:
-            if st["graph"] is None or st["sig"] != self._signature() or st["n_forced"] != n_forced:
-                self._capture(st, n_forced, dev, run=self._beam_run)
-                self._beam_begin(st, prompt)
-            st["graph"].replay()
-        else:
-            self._beam_run(st, n_forced, eager=True)
-        bs = st["beam"]
-        n = int(bs["fin_len"][:, 0].max())  # transformers counts the entries of the chosen hypotheses' beam trail
-        self.sequences_scores = bs["fin_score"][:, 0].clone()
-        return bs["fin_seq"][:, 0, :len(prompt) + n].long().cpu().contiguous()
 
     @torch.no_grad()
     def _forward_logits(self, pixel_values, forced_ids):
@@ -883,13 +814,13 @@ class BlipForConditionalGeneration(Bk.CachedWeights, nn.Module):
         B, Tn = ids.shape
         if Tn + 1 > self.config.text.max_position_embeddings:
             raise ValueError("forced_ids is longer than the position table")
-        st = self._state(B, Tn, dev)
+        mode = _Greedy()
+        st = self._state(mode, B, Tn, dev)
         st["px"].copy_(pixel_values.to(dev).float())
-        st["forced"].zero_()
-        st["forced"][:Tn] = ids.t()
-        self._begin(st, st["forced"][0])
+        st["mode"] = mode
+        mode.begin(self, st, ids.t())
         logits = torch.empty(Tn, B, self.config.text.vocab_size, device=dev, dtype=torch.float32)
-        self._run(st, Tn, logits=logits)
+        self._run(st, Tn, logits=logits, sc=sc)
         return logits
 
     def forward_logits(self, pixel_values, forced_ids):

@@ -23,6 +23,17 @@ def load_fixture():
     return z, cfg, W
 
 
+def load_model(cfg, W, precision="fp32", device="cuda"):
+    """mmfd's BlipForConditionalGeneration with the fixture's weights, frozen, on `device` in `precision`"""
+    from mmfd.blip import BlipConfig, BlipForConditionalGeneration
+    m = BlipForConditionalGeneration(BlipConfig(vision=cfg["vision"], text=cfg["text"]))
+    res = m.load_state_dict(W, strict=True)
+    assert not res.missing_keys and not res.unexpected_keys
+    for p in m.parameters():
+        p.requires_grad_(False)
+    return m.to(device).eval().set_precision(precision)
+
+
 def live_mask(seq, eos):
     """[steps, B] bool: row b has not produced eos before step t (seq [B, 1 + steps], bos first)"""
     seq = np.asarray(seq)

@@ -291,12 +291,7 @@ def fx():
 
 
 def _model(fx, precision="fp32"):
-    from mmfd.blip import BlipConfig, BlipForConditionalGeneration
-    m = BlipForConditionalGeneration(BlipConfig(vision=fx["cfg"]["vision"], text=fx["cfg"]["text"]))
-    m.load_state_dict(fx["W"], strict=True)
-    for p in m.parameters():
-        p.requires_grad_(False)
-    return m.to(DEV).eval().set_precision(precision)
+    return R.load_model(fx["cfg"], fx["W"], precision, DEV)
 
 
 @pytest.fixture(scope="module")
